@@ -12,7 +12,19 @@ Workloads (BASELINE.json configs):
   point_mass                 the analytic bring-up plugin, 1024 x 32 (configs[1])
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload point_mass]
+    python bench.py --full ...                        (the plain line + everything measured beside it)
+    python bench.py --dump-outputs DIR ...            (the last timed update's results as DIR/*.npy)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
+
+A plain run sets up, warms up, times the --steps updates and prints the result line (metric, value,
+unit, ms_per_step, the configuration, the engine's own report of its launch, the RCCL check).  What
+takes further runs or work of its own is behind --full: the rollout launch's roofline and the HBM
+view (further eager updates under --graph 1, five untimed updates with every event recorded, the
+recorded PMC traffic) and the CPU baseline (the oracle, compiled for the host and timed).  The timed
+loop is the same in both, its sampled rollout-launch events included, so `value` does not depend on
+--full.  --dump-outputs DIR writes what the last timed update left for its caller (the optimal
+rollout U*, the costs, the weights, the gradient) as float64 DIR/<name>.npy; the state, the forecast
+and the Philox seed are constants, so the same arguments give the same inputs in every run.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N rank processes
 itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one GPU each) before anything imports the
@@ -86,7 +98,11 @@ def parse():
     p.add_argument("--horizon-steps", type=int, default=None,
                    help="H (dt = 0.01); 64 = configs[2]/[3], 128 = configs[4]; 32 for point_mass")
     p.add_argument("--smoothing", type=int, default=0, help="Savitzky-Golay window (order 1); 10 = configs[4]")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: kernel breakdown, roofline, HBM view, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed update's U*, costs, weights and gradient as DIR/<name>.npy (float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="threads of the CPU baseline (0: the CPU share this process may use)")
     p.add_argument("--cpu-updates", type=int, default=50, help="timed CPU updates (median / p90), BASELINE.md §2")
@@ -282,6 +298,74 @@ def bootstrap_only(world, rank, local_rank, dist):
     dist.destroy_process_group()
 
 
+def max_over_ranks(dist, elapsed):
+    """The timed region's seconds: the slowest rank's (gloo), this process's own at N = 1."""
+    if not dist:
+        return elapsed
+    dist.barrier()
+    import torch
+    t = torch.tensor([elapsed], dtype=torch.float64)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return float(t.item())
+
+
+DUMP_BYTES = 15 * 2 ** 20  # per array: four arrays stay under 64 MB in all
+
+
+def dump_outputs(traj, directory):
+    """--dump-outputs: what the last timed update left for its caller, as float64 DIR/<name>.npy,
+    read after the closing synchronize and before any further update.  An array above DUMP_BYTES is
+    cut to a fixed sample (the sorted indices of a generator seeded with 0, the same in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"optimal_rollout": traj.get_optimal_rollout(),   # U*, (H, C)
+              "costs": traj.costs(),                           # (R,)
+              "weights": traj.get_weights(),                   # (R,)
+              "gradient": traj.get_gradient()}                 # (H, C)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > DUMP_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_BYTES // 8, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def result_line(args, pm, sg, world, comm1, S_total, H, ms_per_step, value, info, rccl):
+    """The line every run prints: the headline figure, the run's shape, the engine's report of its
+    rollout launch and the RCCL check.  --full adds its measurements to it."""
+    label = workload_label(pm, S_total, H, args.smoothing if sg else 0, world, args.graph)
+    if pm:
+        workload = "%s%d samples x %d horizon, point-mass analytic dynamics + quadratic cost" % (label, S_total, H)
+        metric = "MPPI rollouts/sec (samples x horizon steps/s), %dx%d point mass" % (S_total, H)
+        data = "synthetic (x0 = 0, target (1,1,1), Philox noise)"
+    else:
+        workload = "%s%d samples x %d horizon, FrankaRidgeback Pinocchio dynamics, full AssistedManipulation cost stack%s%s%s" % (
+            label, S_total, H,
+            ", Savitzky-Golay window %d order 1" % args.smoothing if sg else "",
+            ", sample-sharded over RCCL" if world > 1 else (", through a one-rank RCCL communicator" if comm1 else ""),
+            ", hipGraph-captured update" if args.graph == 1 else "")
+        metric = "MPPI rollouts/sec (samples x horizon steps/s), %dx%d FrankaRidgeback" % (S_total, H)
+        data = "synthetic (HUDDLED state, constant forecast wrench (20,0,0) N, Philox noise)"
+    return {
+        "metric": metric,
+        "value": value,
+        "unit": "rollout-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": data,
+        "full": bool(args.full),
+        "config": {"workload": workload, "samples": S_total, "horizon": H, "keep_best": KEEP_BEST,
+                   "parallelism": "samples-dp%d" % world, "graph": args.graph, "comm1": int(comm1)},
+        "engine": info,
+        "rccl": rccl,
+    }
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -396,6 +480,21 @@ def run(args, world, rank, local_rank, dist):
     graph_timed = traj.graph_updates() - g0   # updates of the timed loop that ran as the hipGraph
     info = traj.update_info()      # what the engine's rollout launch did (its own choice, not re-derived)
     info["graph_updates_timed"] = graph_timed
+    if args.dump_outputs and rank == 0:   # (every rank holds the all-reduced costs and U*)
+        dump_outputs(traj, args.dump_outputs)
+    if not args.full:   # the plain run ends here: nothing further is launched or measured
+        elapsed = max_over_ranks(dist, elapsed)
+        if rank == 0:
+            line = result_line(args, pm, sg, world, comm1, S_total, traj.H, 1000.0 * elapsed / args.steps,
+                               S_total * traj.H / (elapsed / args.steps), info, rccl)
+            dyn_times = traj.rollout_kernel_times()   # the events the timed loop sampled (none with --graph 1)
+            if dyn_times:
+                line["kernel_ms"] = {"rollout_launch": sum(dyn_times) / len(dyn_times),
+                                     "rollout_launch_samples": len(dyn_times)}
+            print(json.dumps(line))
+        if dist:
+            dist.destroy_process_group()
+        return
     ev_source = "HIP events on every %d-th timed update" % EV_EVERY
     if not sample_events:   # the graph path: the rollout launch timed over further eager updates
         traj.set_timing(1)
@@ -416,12 +515,7 @@ def run(args, world, rank, local_rank, dist):
         j += 1
     kt /= nb
     kt[3] = traj.kernel_times()[3]   # the optimal rollout (side stream) of the last update
-    if dist:
-        dist.barrier()
-        import torch
-        t = torch.tensor([elapsed], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    elapsed = max_over_ranks(dist, elapsed)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = S_total * traj.H / (elapsed / args.steps)
     count_local = traj.R // world + (1 if rank < traj.R % world else 0)
@@ -516,42 +610,12 @@ def run(args, world, rank, local_rank, dist):
         if dist:
             dist.destroy_process_group()
         return
-    label = workload_label(pm, S_total, traj.H, args.smoothing if sg else 0, world, args.graph)
-    if pm:
-        workload = "%s%d samples x %d horizon, point-mass analytic dynamics + quadratic cost" % (label, S_total, traj.H)
-        metric = "MPPI rollouts/sec (samples x horizon steps/s), %dx%d point mass" % (S_total, traj.H)
-        data = "synthetic (x0 = 0, target (1,1,1), Philox noise)"
-    else:
-        workload = "%s%d samples x %d horizon, FrankaRidgeback Pinocchio dynamics, full AssistedManipulation cost stack%s%s%s" % (
-            label, S_total, traj.H,
-            ", Savitzky-Golay window %d order 1" % args.smoothing if sg else "",
-            ", sample-sharded over RCCL" if world > 1 else (", through a one-rank RCCL communicator" if comm1 else ""),
-            ", hipGraph-captured update" if args.graph == 1 else "")
-        metric = "MPPI rollouts/sec (samples x horizon steps/s), %dx%d FrankaRidgeback" % (S_total, traj.H)
-        data = "synthetic (HUDDLED state, constant forecast wrench (20,0,0) N, Philox noise)"
-    line = {
-        "metric": metric,
-        "value": value,
-        "unit": "rollout-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": data,
-        "config": {"workload": workload, "samples": S_total, "horizon": traj.H, "keep_best": KEEP_BEST,
-                   "parallelism": "samples-dp%d" % world, "graph": args.graph, "comm1": int(comm1)},
-        "engine": info,
-        "kernel_ms": {"rollout_launch": dyn_ms, "rollout_launch_samples": len(dyn_times), "breakdown_untimed": {
-                      "sample": kt[0], "rollout": kt[1], "reduce": kt[2], "weights_gradient": kt[6],
-                      "cost_allreduce": kt[7], "optimal_rollout": kt[3], "update": kt[4]}},
-        "roofline": roofline,
-        "hbm": hbm,
-        "rccl": rccl,
-    }
+    line = result_line(args, pm, sg, world, comm1, S_total, traj.H, ms_per_step, value, info, rccl)
+    line["kernel_ms"] = {"rollout_launch": dyn_ms, "rollout_launch_samples": len(dyn_times), "breakdown_untimed": {
+                         "sample": kt[0], "rollout": kt[1], "reduce": kt[2], "weights_gradient": kt[6],
+                         "cost_allreduce": kt[7], "optimal_rollout": kt[3], "update": kt[4]}}
+    line["roofline"] = roofline
+    line["hbm"] = hbm
     if not args.no_cpu_baseline:   # rank 0, after the timed loop: the whole job's workload
         line["cpu_baseline"] = cpu_baseline(args, pm, world)
         # not vs_baseline (no published number): the GPU / CPU-port ratio, same workload

@@ -5,14 +5,17 @@ returns is a fixed placeholder; nothing here is measured."""
 import math
 import os
 
+import numpy as np
+
 
 def comm_unique_id():
     return os.urandom(128)
 
 
 class StubTrajectory:
-    def __init__(self, conf, world, rank):
+    def __init__(self, conf, world, rank, control_dof):
         self.R = conf.rollouts + 2
+        self.C = control_dof
         self.H = int(math.ceil(conf.horison / conf.time_step))   # mppi.cpp:85
         self.world, self.rank = world, rank
         self.graph = 0
@@ -75,9 +78,23 @@ class StubTrajectory:
     def _check(self, st):
         assert st == 0
 
+    # what --dump-outputs reads: placeholders that depend on the number of updates made, so that a
+    # dump taken after a further update would differ
+    def get_optimal_rollout(self):
+        return np.full((self.H, self.C), float(self.updates))
+
+    def get_gradient(self):
+        return np.full((self.H, self.C), 0.5 * self.updates)
+
+    def costs(self):
+        return np.arange(self.R, dtype=np.float64) + self.updates
+
+    def get_weights(self):
+        return np.full(self.R, 1.0 / self.R)
+
 
 def creator(world, rank):
     def create(conf, dynamics, cost, device=0):
         assert device == rank
-        return StubTrajectory(conf, world, rank)
+        return StubTrajectory(conf, world, rank, dynamics.get_control_dof())
     return create

@@ -728,8 +728,26 @@ def gen_updates(rob, S, K, H, updates, seed, smoothing=None, track_point=False, 
     return out
 
 
+def gravity_gradient(rob, q, h=1e-6):
+    """dV/dq of V = sum m g z_com over every link with mass, by central differences of step h."""
+    def V(qq):
+        e = 0.0
+        for link, (m, c, I) in rob.inertial.items():
+            T = rob.frame(qq, link)
+            e += m * 9.81 * (T[:3, 3] + T[:3, :3] @ c)[2]
+        return e
+    n = len(q)
+    return np.array([(V(q + h * np.eye(n)[i]) - V(q - h * np.eye(n)[i])) / (2 * h) for i in range(n)])
+
+
 def main():
     rob = Robot()
+    if "--gravity" in sys.argv or not os.path.exists(os.path.join(HERE, "gravity.npz")):
+        print("gravity fixture (potential gradient at the huddled configuration)")
+        q = huddled()[:12]
+        np.savez_compressed(os.path.join(HERE, "gravity.npz"), q=q, grad=gravity_gradient(rob, q))
+        if "--gravity" in sys.argv:
+            return
     if "--kalman" in sys.argv or not os.path.exists(os.path.join(HERE, "kalman.npz")):
         print("Kalman forecast fixtures (orders 1, 2)")
         k1, k2 = gen_kalman(1, 41), gen_kalman(2, 42)

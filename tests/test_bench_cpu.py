@@ -70,8 +70,8 @@ def test_bench_line_schema_at_two_ranks():
     """The N > 1 line on a stand-in engine (tests/bench_stub.py): rank 0 times
     the CPU baseline on the whole job's workload after the timed loop, the weight reduce is reported
     without the cost all-reduce (timed beside it), and the RCCL check and labels hold."""
-    d = _stub_line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--samples-per-gpu", "64", "--horizon-steps", "8",
-                    "--cpu-updates", "2", "--cpu-warmup", "1"])
+    d = _stub_line(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--samples-per-gpu", "64",
+                    "--horizon-steps", "8", "--cpu-updates", "2", "--cpu-warmup", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "hbm", "rccl"):
         assert k in d, k
@@ -91,12 +91,40 @@ def test_bench_graph_mode_times_every_update_as_the_graph():
     """--graph 1 (with --comm1: the sharded path through a one-rank communicator): the timed loop
     records no timing events, so every timed update can replay the graph (graph_updates_timed ==
     steps); the rollout launch is timed over eager updates after the loop."""
-    d = _stub_line(["--steps", "5", "--warmup", "2", "--samples-per-gpu", "64", "--horizon-steps", "8", "--graph", "1",
-                    "--comm1", "1", "--no-cpu-baseline"])
+    d = _stub_line(["--full", "--steps", "5", "--warmup", "2", "--samples-per-gpu", "64", "--horizon-steps", "8",
+                    "--graph", "1", "--comm1", "1", "--no-cpu-baseline"])
     assert d["engine"]["graph_updates_timed"] == 5
     assert d["config"]["comm1"] == 1 and "one-rank RCCL" in d["config"]["workload"]
     assert "eager updates after the timed (graph) loop" in d["roofline"]["launch_time_source"]
     assert d["kernel_ms"]["rollout_launch_samples"] > 0
+
+
+def test_bench_plain_run_stops_after_the_timed_steps(tmp_path):
+    """Without --full the run makes warmup + steps updates and no more (the stand-in counts them),
+    prints the headline's fields without the roofline, the HBM view or the CPU baseline, and
+    --dump-outputs writes what the last timed update left, as float64 arrays."""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--samples-per-gpu", "64", "--horizon-steps", "8",
+            "--dump-outputs", str(tmp_path / "out")]
+    d = _stub_line(args)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config",
+              "engine", "rccl"):
+        assert k in d, k
+    for k in ("roofline", "hbm", "cpu_baseline", "speedup_vs_cpu_baseline"):
+        assert k not in d, k
+    assert d["full"] is False and d["steps"] == 5 and d["engine"]["update_count"] == 7
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 64 * 8 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert d["kernel_ms"]["rollout_launch_samples"] == 1   # the timed loop's sampled events, read after it
+    out = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("optimal_rollout", "costs", "weights", "gradient")}
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(n + ".npy" for n in out)
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["optimal_rollout"].shape == out["gradient"].shape == (8, 12)
+    assert out["costs"].shape == out["weights"].shape == (66,)
+    assert np.all(out["optimal_rollout"] == 7.0) and out["costs"][0] == 7.0   # the state after the last timed update
+    # --full goes on measuring after the loop; the dump is still the last timed update's
+    f = _stub_line(["--full", "--no-cpu-baseline"] + args)
+    assert f["full"] is True and "roofline" in f and f["engine"]["update_count"] == 7
+    assert np.all(np.load(tmp_path / "out" / "optimal_rollout.npy") == 7.0)
 
 
 def test_bench_workload_labels():

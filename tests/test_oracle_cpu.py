@@ -53,23 +53,13 @@ def test_aba_of_nle_is_zero(model):
 
 
 def test_gravity_torque_matches_potential_gradient(model):
-    """nle(q, 0) = dV/dq with V = sum m g z_com (numpy model, finite differences)."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from gen_golden import Robot
-    rob = Robot()
+    """nle(q, 0) = dV/dq with V = sum m g z_com (numpy model, finite differences: gravity.npz,
+    gen_golden.gravity_gradient at the huddled configuration)."""
+    g = load("gravity.npz")
     q = am.huddled_state()[:12]
-
-    def V(qq):
-        e = 0.0
-        for link, (m, c, I) in rob.inertial.items():
-            T = rob.frame(qq, link)
-            e += m * 9.81 * (T[:3, 3] + T[:3, :3] @ c)[2]
-        return e
-    h = 1e-6
-    grad = np.array([(V(q + h * np.eye(12)[i]) - V(q - h * np.eye(12)[i])) / (2 * h) for i in range(12)])
+    np.testing.assert_array_equal(g["q"], q)   # the fixture is for this configuration
     k = O.kinematics(model, q, np.zeros(12), np.zeros(12), 0)
-    np.testing.assert_allclose(k["nle"], grad, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(k["nle"], g["grad"], rtol=0, atol=1e-6)
 
 
 def test_nle_against_complex_step_lagrangian(model):

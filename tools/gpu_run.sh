@@ -9,7 +9,7 @@
 #   smoke              __graft_entry__.smoke()
 #   tests[:EXPR]       the whole -m gpu suite in one pytest process (or -k EXPR)
 #   softtests[:EXPR]   the same, but test failures (not crashes or timeouts) let the later steps run
-#   bench              the default bench line (N = 1, with the CPU baseline)
+#   bench              bench.py --full: the default line (N = 1) with the roofline and the CPU baseline
 #   trace[:NAME]       rocprofv3 --kernel-trace --stats of the bench (no CPU baseline; BENCH_ARGS apply;
 #                      NAME names the output, default "trace")
 #   tracepm            trace of the point-mass workload (configs[1]), 200 updates
@@ -67,7 +67,7 @@ step_tests() {   # [expr] [soft]: soft = test failures (pytest rc 1) do not stop
 }
 
 step_bench() {
-    timeout -k 10 300 python -u bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err \
+    timeout -k 10 300 python -u bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err \
         || { echo "bench rc=$?"; tail -20 $O/bench.err; return 1; }
     summary $O/bench.json bench
 }
@@ -75,7 +75,7 @@ step_bench() {
 step_trace() {   # [name] [extra bench args...]
     local n=${1:-trace}; shift
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$n -o run --output-format csv -- \
-        python3 bench.py --no-cpu-baseline $BENCH_ARGS "$@" > $O/${n}_bench.json 2> $O/$n.err \
+        python3 bench.py --full --no-cpu-baseline $BENCH_ARGS "$@" > $O/${n}_bench.json 2> $O/$n.err \
         || { echo "trace rc=$?"; tail -20 $O/$n.err; return 1; }
     summary $O/${n}_bench.json $n
     local st
@@ -88,12 +88,12 @@ step_trace() {   # [name] [extra bench args...]
 }
 
 step_pmc() {   # [pm | NAME PREFIX]: NAME: a size's passes (BENCH_ARGS) into $O/pmc_NAME, the kernel matched by PREFIX
-    local B="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline $BENCH_ARGS" D=$O/pmc out=$O/pmc_rollout.json prefix=
+    local B="python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline $BENCH_ARGS" D=$O/pmc out=$O/pmc_rollout.json prefix=
     if [ -n "$2" ]; then
         D=$O/pmc_$1 out=$O/pmc_$1.json prefix=$2
     fi
     if [ "$1" = pm ]; then
-        B="python3 bench.py --workload point_mass --steps 50 --warmup 5 --no-cpu-baseline"
+        B="python3 bench.py --workload point_mass --steps 50 --warmup 5 --full --no-cpu-baseline"
         D=$O/pmcpm out=$O/pmc_pm.json prefix=pm_update_kernel
     fi
     mkdir -p $D
@@ -122,7 +122,7 @@ step_kpmc() {   # V1,V2,..: counters of the kernels outside the rollout launch, 
         local lib=$PWD/gpurun_variants/$v/libmppi_amd.so D=$O/kpmc_$v
         [ "$v" = tree ] && lib=$PWD/assistedmanipulation_amd/lib/libmppi_amd.so
         mkdir -p $D
-        local B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+        local B="python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline"
         krun() {   # name counters...
             local n=$1; shift
             MPPI_AMD_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-trace --kernel-include-regex "weights|finish|rank_draw" \
@@ -138,7 +138,7 @@ step_kpmc() {   # V1,V2,..: counters of the kernels outside the rollout launch, 
 step_sizes() {
     size() {   # name args...
         local n=$1; shift
-        timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" > $O/size_$n.json 2> $O/size_$n.err \
+        timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" > $O/size_$n.json 2> $O/size_$n.err \
             || { echo "size $n rc=$?"; tail -5 $O/size_$n.err; return 1; }
         summary $O/size_$n.json $n
     }
@@ -153,7 +153,7 @@ step_graphab() {   # [rounds]: configs[4]'s shapes, the hipGraph against eager l
     local rounds=${1:-2} i
     gsize() {   # name args...
         local n=$1; shift
-        timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" > $O/size_$n.json 2> $O/size_$n.err \
+        timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" > $O/size_$n.json 2> $O/size_$n.err \
             || { echo "size $n rc=$?"; tail -5 $O/size_$n.err; return 1; }
         summary $O/size_$n.json $n
         python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().split(chr(10))[-1]); print('   graph_updates_timed', d['engine']['graph_updates_timed'], 'of', d['steps'])" $O/size_$n.json
@@ -183,7 +183,7 @@ step_absizes() {   # V1,V2,..  rounds: interleaved A/B of the library variants o
                 local lib=$PWD/assistedmanipulation_amd/lib/libmppi_amd.so n=${w%%:*} f
                 case $v in tree*) ;; *) lib=$PWD/gpurun_variants/$v/libmppi_amd.so;; esac
                 f=$O/abs_${n}_${v}_$i.json
-                MPPI_AMD_LIB=$lib timeout -k 10 200 python -u bench.py --no-cpu-baseline ${w#*:} > $f 2> ${f%.json}.err \
+                MPPI_AMD_LIB=$lib timeout -k 10 200 python -u bench.py --full --no-cpu-baseline ${w#*:} > $f 2> ${f%.json}.err \
                     || { echo "absizes $n $v rc=$?"; tail -20 ${f%.json}.err; return 1; }
                 summary $f "$n/$v/$i"
             done
@@ -199,7 +199,7 @@ step_ab() {   # V1,V2,..  rounds
             local lib=$PWD/assistedmanipulation_amd/lib/libmppi_amd.so
             case $v in tree*) ;; *) lib=$PWD/gpurun_variants/$v/libmppi_amd.so;; esac
             local envv="AB_ENV_$v" f=$O/ab_${v}_$i.json
-            env MPPI_AMD_LIB=$lib ${!envv} timeout -k 10 200 python -u bench.py --no-cpu-baseline $BENCH_ARGS \
+            env MPPI_AMD_LIB=$lib ${!envv} timeout -k 10 200 python -u bench.py --full --no-cpu-baseline $BENCH_ARGS \
                 > $f 2> $O/ab_${v}_$i.err || { echo "ab $v rc=$?"; tail -20 $O/ab_${v}_$i.err; return 1; }
             summary $f "$v/$i"
         done
@@ -210,7 +210,7 @@ step_pmstamps() {   # [variant]: the fused point-mass kernel's phase stamps (MPP
     local lib=$PWD/assistedmanipulation_amd/lib/libmppi_amd.so n=pmstamps${1:+_$1}
     [ -n "$1" ] && lib=$PWD/gpurun_variants/$1/libmppi_amd.so
     MPPI_AMD_LIB=$lib MPPI_PM_STAMPS=1 timeout -k 10 200 python -u bench.py --workload point_mass --steps 100 --warmup 10 \
-        --no-cpu-baseline > $O/$n.json 2> $O/$n.err || { echo "$n rc=$?"; tail -20 $O/$n.err; return 1; }
+        --full --no-cpu-baseline > $O/$n.json 2> $O/$n.err || { echo "$n rc=$?"; tail -20 $O/$n.err; return 1; }
     grep "pm_update_kernel phases" $O/$n.err
     summary $O/$n.json $n
 }
@@ -219,7 +219,7 @@ step_pmstamps() {   # [variant]: the fused point-mass kernel's phase stamps (MPP
 step_wtrace() {   # variant
     local lib=$PWD/gpurun_variants/$1/libmppi_amd.so
     MPPI_WAVE_TRACE=$PWD/$O/wt.bin MPPI_AMD_LIB=$lib timeout -k 10 120 python bench.py --steps 40 --warmup 10 \
-        --no-cpu-baseline $BENCH_ARGS > $O/wt.json 2> $O/wt.err || { echo "wtrace rc=$?"; tail $O/wt.err; return 1; }
+        --full --no-cpu-baseline $BENCH_ARGS > $O/wt.json 2> $O/wt.err || { echo "wtrace rc=$?"; tail $O/wt.err; return 1; }
     python3 tools/wave_trace_r06.py $O/wt.bin 1064 | tee $O/wave_trace.txt
 }
 
