@@ -88,13 +88,12 @@ struct mppi_handle {
     hipEvent_t ev_ring[2 * EV_RING] = {};
     int ring_head = 0, ring_count = 0;   // next pair to record; recorded pairs not yet read
     bool ring_unread = false;            // kernel_ms[5] not yet taken from the newest pair
-    // the update's rollout launch drew the next update's eps for its main waves' rows (tail_draws):
-    // phase 3 draws only the rows it left (launch_draw_ahead's subset)
-    bool tail_drawn = false;
+    // the shape of the update's rollout launch (coop_plan.hpp), decided once in phase 1.  tail_draws:
+    // it drew the next update's eps for its main waves' rows, and phase 3 draws only the rows it left
+    // (launch_draw_ahead's subset, plan.tail)
+    CoopPlan plan{};
     // what the last update's rollout launch did (mppi_update_info)
     int64_t info[MPPI_UPDATE_INFO_N] = {};
-    int tail_nxb = 0;
-    int64_t tail_xbase = 0, tail_row0 = 0;
     // MPPI_HOST_TRACE=1: host-side turnaround stamps, averaged and printed by mppi_destroy:
     // [0] flag seen -> phase 3 returns, [1] return -> next phase 1, [2] phase 1 -> rollout launched
     bool host_trace = false;
@@ -195,12 +194,10 @@ struct mppi_handle {
     int graph_mode = 0;
     bool graph_dry = false;             // phases fill `gargs` instead of launching
     struct GraphArgs {
-        FrRolloutArgs roll, roll2;   // the rollout launch (the split's two: roll, roll2)
-        int nroll = 1;
+        FrRolloutArgs roll[2];   // the rollout launch (the split's two), plan.nlaunch of them
         WGradArgs wg;
         FinishArgs fin;
         RankDrawLaunch rd;
-        bool x_kernel = false, folded = false;
     } gargs;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -495,7 +492,7 @@ mppi_status check_topology(const mppi_frankaridgeback_desc &d, std::string &why)
     }
     // The planar base's x / y joints sit unrotated on the world (robot.urdf x_base_joint /
     // y_base_joint, rpy 0 0 0): the solve takes their motion subspaces as the unit axes
-    // (column_dots, and the zero M_01 of gj_pivot_0).
+    // (column_dots, and the zero M_01 of gj_rows).
     for (int i = 0; i < 2; i++)
         for (int k = 0; k < 9; k++)
             if (d.bodies[i].rotation[k] != ((k % 4 == 0) ? 1.0 : 0.0)) {
@@ -536,7 +533,7 @@ static bool draw_ahead_possible(const mppi_handle *h)
 {
     if (h->env.draw_ahead_off) return false;
     return h->dyn_kind == MPPI_DYNAMICS_FRANKARIDGEBACK && h->C == FR_C && h->tdiag &&
-           h->noise_source == MPPI_NOISE_DEVICE_PHILOX && fr_coop_update_fusable(h->count, h->env);
+           h->noise_source == MPPI_NOISE_DEVICE_PHILOX && coop_fusable(h->count, h->env);
 }
 
 // MPPI_TAIL_DRAWS=0: the next update's draws all in rank_draw_kernel behind the publish (A/B)
@@ -1561,7 +1558,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
     if (!h || !state) return MPPI_ERR_INVALID;
     HIP_TRY(hipSetDevice(h->device));
     h->t_start = std::chrono::steady_clock::now();
-    h->tail_drawn = false;
+    h->plan.tail_draws = false;
     if (h->host_trace && h->ht_n[0] > h->ht_n[1]) {
         h->ht_sum[1] += std::chrono::duration<double, std::micro>(h->t_start - h->ht_ret).count();
         h->ht_n[1]++;
@@ -1690,34 +1687,28 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
             a.fcost = h->d_opt;
             a.frec = h->d_rec_opt;
         }
-        bool folded = false, costs_done = false, tail = false;
-        CoopTail ct;
         a.stats = cost_stats_used(h) ? h->d_cstats : nullptr;
         // the next update's draws in the launch's tail, into the buffer it will write (phase 3 makes
         // the rest with the rank); needs the draws made ahead and no tail switch-off
         a.ahead_noise = (ahead && !tail_draws_disabled(h)) ? h->d_noise_prev : nullptr;
-        HIP_TRY(launch_fr_coop_update(a, h->env, h->stream, ev_in_launch ? ev_r0 : nullptr, ev_in_launch ? ev_r1 : nullptr,
-                                      &folded, &costs_done, &tail, &h->gargs.roll, &h->gargs.x_kernel, h->graph_dry, &ct,
-                                      &h->gargs.roll2));
-        h->gargs.folded = folded;
-        h->gargs.nroll = ct.launches;
+        h->plan = coop_plan(a.count, a.H, fold, ahead, a.ahead_noise != nullptr, a.rx != nullptr, h->env);
+        const CoopPlan &plan = h->plan;
+        if (plan.error) HIP_TRY(hipErrorInvalidValue);
+        if (h->graph_dry)
+            for (int i = 0; i < plan.nlaunch; i++) h->gargs.roll[i] = fr_coop_launch_args(a, plan, i);
+        else HIP_TRY(launch_fr_coop_update(a, plan, h->stream, ev_in_launch ? ev_r0 : nullptr, ev_in_launch ? ev_r1 : nullptr));
+        const bool folded = plan.folded, costs_done = plan.costs_in_launch;
         if (h->timing >= 2) HIP_TRY(hipEventRecord(h->ev_dyn, h->stream));
         if (!folded) a.fcost = nullptr;
         // fr_coop_x_kernel (the rows left over, the split) writes 768-B records, fr_coop_kernel compact ones
-        if (!costs_done && !h->graph_dry) HIP_TRY(launch_fr_step_cost(cost_args(h, a, !h->gargs.x_kernel), h->stream));
-        h->tail_drawn = tail;
+        if (!costs_done && !h->graph_dry) HIP_TRY(launch_fr_step_cost(cost_args(h, a, !plan.x_kernel), h->stream));
         h->info[MPPI_INFO_COOPERATIVE] = 1;
         h->info[MPPI_INFO_FOLDED_FILTER] = folded ? 1 : 0;
         h->info[MPPI_INFO_OBJECTIVE_IN_LAUNCH] = costs_done ? 1 : 0;
-        h->info[MPPI_INFO_TAIL_DRAWS] = tail ? 1 : 0;
+        h->info[MPPI_INFO_TAIL_DRAWS] = plan.tail_draws ? 1 : 0;
         h->info[MPPI_INFO_SAMPLING] = ahead ? 2 : 0;
         h->info[MPPI_INFO_ROWS] = h->count + (folded ? 1 : 0);
-        h->info[MPPI_INFO_HANDOVER] = h->gargs.x_kernel ? -2 : -1;   // -2: read from the device on request
-        if (tail) {   // the rows the launch left to rank_draw_kernel (fr_coop.hip relay_stage, group_draws)
-            h->tail_row0 = ct.row0;
-            h->tail_xbase = ct.xbase;
-            h->tail_nxb = ct.nxb;
-        }
+        h->info[MPPI_INFO_HANDOVER] = plan.x_kernel ? -2 : -1;   // -2: read from the device on request
         if (folded) h->opt_rec_compact = false;   // the folded row: fr_coop_x_kernel's 768-B records
         if (folded) {   // the optimal cost is ready with this update's rollouts; phase 3's host block
                         // carries it back (finish_kernel copies d_opt), on the same stream
@@ -1876,9 +1867,10 @@ static mppi_status phase3_launch(mppi_handle *h, double *seq_out)
         sa.H = (int)h->H;
         sa.C = (int)h->C;
         for (int64_t c = 0; c < h->C && c < FR_C; c++) sa.tdv[c] = h->T[(size_t)(c * h->C + c)];
-        if (h->tail_drawn)
-            HIP_TRY(launch_draw_ahead(sa, h->d_costs, h->S, h->d_rank, h->d_rank_keys, h->stream, h->tail_nxb, h->tail_xbase,
-                                      h->tail_row0, &h->gargs.rd, h->graph_dry));
+        // the rows the launch's tail draws left to rank_draw_kernel (fr_coop.hip relay_stage, group_draws)
+        if (h->plan.tail_draws)
+            HIP_TRY(launch_draw_ahead(sa, h->d_costs, h->S, h->d_rank, h->d_rank_keys, h->stream, h->plan.tail.nxb,
+                                      h->plan.tail.xbase, h->plan.tail.row0, &h->gargs.rd, h->graph_dry));
         else HIP_TRY(launch_draw_ahead(sa, h->d_costs, h->S, h->d_rank, h->d_rank_keys, h->stream, 0, 0, 0, &h->gargs.rd,
                                        h->graph_dry));
         h->ahead = {h->update_count + 1, h->seed, h->begin, h->count, h->H, h->C};
@@ -1996,7 +1988,7 @@ static bool graph_eligible(const mppi_handle *h)
     // the launch path the replayed nodes assume: fr_coop_x_kernel with the filter() row folded and
     // the objective in the launch (a rollout count that is a multiple of 16 takes fr_coop_kernel<4>
     // with filter() left pending, a horizon past 128 steps adds the cost kernel)
-    if (!fr_coop_update_folds(h->count, (int)h->H, h->env) || h->debug_updates > 0) return false;
+    if (!coop_folds(h->count, (int)h->H, h->env) || h->debug_updates > 0) return false;
     return h->ahead_valid && h->ahead.update_index == h->update_count && h->ahead.seed == h->seed &&
            h->ahead.begin == h->begin && h->ahead.count == h->count && h->ahead.H == h->H && h->ahead.C == h->C;
 }
@@ -2039,7 +2031,7 @@ static mppi_status graph_nodes(mppi_handle *h)
     }
     // the launches the arguments are kept for: the rollout launch(es), one weights kernel (and the
     // large-R softmin pair ahead of it), one finish, one rank + draws
-    if (count[GK_ROLLOUT] != h->gargs.nroll || count[GK_WGRAD] < 1 || count[GK_FINISH] != 1 || count[GK_RANKDRAW] != 1)
+    if (count[GK_ROLLOUT] != h->plan.nlaunch || count[GK_WGRAD] < 1 || count[GK_FINISH] != 1 || count[GK_RANKDRAW] != 1)
         return fail(h, MPPI_ERR_DEVICE, "captured update graph has " + std::to_string(count[GK_ROLLOUT]) + " rollout, " +
                                             std::to_string(count[GK_WGRAD]) + " weights, " + std::to_string(count[GK_FINISH]) +
                                             " finish and " + std::to_string(count[GK_RANKDRAW]) + " rank nodes");
@@ -2171,12 +2163,12 @@ static mppi_status update_graph(mppi_handle *h, const double *state, double time
         }
     } else {
         if (st != MPPI_OK) return st;
-        if (!h->gargs.x_kernel || !h->gargs.folded) {   // graph_eligible rules this out; never replay a stale chain
+        if (!h->plan.x_kernel || !h->plan.folded) {   // graph_eligible rules this out; never replay a stale chain
             h->graph_mode = 0;
             return fail(h, MPPI_ERR_DEVICE, "graph update took another launch path");
         }
         RankDrawLaunch &rd = h->gargs.rd;
-        void *aroll[2][1] = {{&h->gargs.roll}, {&h->gargs.roll2}};
+        void *aroll[2][1] = {{&h->gargs.roll[0]}, {&h->gargs.roll[1]}};
         void *awg[] = {&h->gargs.wg};
         void *afin[] = {&h->gargs.fin};
         void *ard[] = {&rd.cost, &rd.S, &rd.rank, &rd.nr, &rd.a, &rd.nx, &rd.sub_nxb, &rd.sub_xbase, &rd.sub_row0};

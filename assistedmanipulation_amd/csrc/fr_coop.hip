@@ -40,6 +40,7 @@
 
 #include "device_common.hpp"
 #include "engine_types.hpp"
+#include "coop_plan.hpp"
 #include "kernels.hpp"
 #include "fr_cost_terms.hpp"
 #include "sample_device.hpp"
@@ -57,13 +58,6 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
-// The body-table fields the step reads stay in registers across the horizon loop (REGTAB, round 6:
-// 789 -> 766 instructions per step, no LDS re-read of the table in every step); -DNO_REGTAB for A/B
-#ifndef NO_REGTAB
-#define REGTAB 1
-// (with it the compiler writes an F operand of column_dots right before the block: one wait state)
-#define COLUMN_DOTS_PAD "s_nop 0\n\t"
-#endif
 #ifdef PHASE_MARKS
 #define PMARK(n) asm volatile("; PHASE " #n)
 #define PMARK_D(n, x) asm volatile("; PHASE " #n : "+v"(x))
@@ -75,7 +69,6 @@ using mppi_dev::smin;
 namespace {
 
 constexpr int ROW = 16;
-constexpr int ROWS_PER_WAVE = 4;
 constexpr int CK_ASSISTED_MANIPULATION = 1, CK_TRACK_POINT = 3;   // mppi_cost_kind
 constexpr int NSLOT = FR_NB + 1;   // + a dummy body slot that lanes 12..15 store into
 
@@ -92,12 +85,11 @@ constexpr int NSLOT = FR_NB + 1;   // + a dummy body slot that lanes 12..15 stor
 constexpr int CSTR = 18;
 constexpr int L_I = 0;
 constexpr int L_COL = 0;                    // no tank: the mass-matrix block (16 x CSTR) over L_I
-constexpr int L_TP = L_COL + 16 * CSTR;     // no tank: the solved right-hand side (12)
 constexpr int L_S = 300;                    // 16-byte aligned; per slot S (6), qd, pad
 constexpr int S_STR = 10;
 // compact records without the tank (store_ks): per slot S linear x, y, z and qd, 48 B apart (the
 // sixteen lanes' 16-byte stores start at 12 j (mod 64) dwords: disjoint bank groups); past the
-// dummy lanes' 0 / 1 at L_TP + 12, 13 (with the tank store_ks reads coop_aba's L_S slots)
+// mass-matrix block (with the tank store_ks reads coop_aba's L_S slots)
 constexpr int L_KS = 304;
 constexpr int KS_STR = 6;
 constexpr int LDS_KIN = 432;                // >= L_S + NSLOT * S_STR, = 16 (mod 32) doubles
@@ -109,10 +101,8 @@ constexpr int L_QDD = L_DU + FR_NB * 2;
 constexpr int L_TAU = L_QDD + ROW;
 constexpr int LDS_SCR = 272;                // >= L_TAU + ROW, = 16 (mod 32) doubles
 static_assert(L_I + NSLOT * 21 <= L_S && L_S + NSLOT * S_STR <= LDS_KIN && L_TAU + ROW <= LDS_SCR, "LDS row layout");
-// (L_TP + 12, 13: the dummy lanes' 0 / 1, over L_S, which only the tank's articulated-body pass uses)
-static_assert(L_TP + 14 <= LDS_KIN && L_TP % 2 == 0, "LDS row layout (mass-matrix block)");
 static_assert(L_S + NSLOT * S_STR <= L_F && L_F + NSLOT * 6 <= LDS_KIN_EN && L_F % 2 == 0, "LDS row layout (energy)");
-static_assert(L_TP + 14 <= L_KS && L_KS % 2 == 0 && L_KS + NSLOT * KS_STR <= LDS_KIN, "LDS row layout (kinematic sums)");
+static_assert(L_COL + 16 * CSTR + 14 <= L_KS && L_KS % 2 == 0 && L_KS + NSLOT * KS_STR <= LDS_KIN, "LDS row layout (kinematic sums)");
 static_assert(LDS_KIN % 32 == 16 && LDS_SCR % 32 == 16 && LDS_KIN_EN % 32 == 16, "row stride bank offset");
 
 // Per-block body table (doubles per body): scan placement R p (body 11: relative to body 10),
@@ -289,12 +279,9 @@ __device__ __forceinline__ void column_dots(const double *S, const double *F, do
     m[1] = F[1];
 #pragma unroll
     for (int i = 2; i < 11; i++) m[i] = 0.0;
-    // no leading s_nop: S (the DPP sources) was formed long before (tools/dpp_hazard_check.py
-    // checks every build's assembly; COLUMN_DOTS_PAD where a build puts an F write right before)
-#ifndef COLUMN_DOTS_PAD
-#define COLUMN_DOTS_PAD ""
-#endif
-    asm(COLUMN_DOTS_PAD
+    // S (the DPP sources) was formed long before; s_nop 0: the compiler writes an F operand right
+    // before the block, one wait state short (tools/dpp_hazard_check.py checks every build's assembly)
+    asm("s_nop 0\n\t"
         "v_fmac_f64_dpp %0, %8, %14 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %1, %8, %14 row_newbcast:3 row_mask:0xf bank_mask:0xe\n\t"
         "v_fmac_f64_dpp %2, %8, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
@@ -346,217 +333,6 @@ __device__ __forceinline__ void column_dots(const double *S, const double *F, do
         : "+&v"(m[2]), "+&v"(m[3]), "+&v"(m[4]), "+&v"(m[5]), "+&v"(m[6]), "+&v"(m[7]), "+&v"(m[8]), "+&v"(m[9])
         : "v"(S[0]), "v"(S[1]), "v"(S[2]), "v"(S[3]), "v"(S[4]), "v"(S[5]), "v"(F[0]), "v"(F[1]), "v"(F[2]), "v"(F[3]), "v"(F[4]), "v"(F[5]));
 }
-// The twelve pivots of the Gauss-Jordan elimination, software-pipelined (pivot k's block
-// updates row k + 1 first and interleaves pivot k + 1's reciprocal chain between its other
-// FMAs), in one asm statement: nt is pivot 0's quotient, inv_next 1 / M[1][1]
-__device__ __forceinline__ void gj_solve(double *Mc, double nt, double inv_next)
-{
-    double qa, qb, d, r, t, e;
-    // s_nop 1: nt (a source of pivot 0's DPP FMAs) may be written right before the block
-    asm("s_nop 1\n\t"
-        /* pivot 0 */
-        "v_fmac_f64_dpp %2, %2, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %12, -%1, %19\n\t"
-        "v_fmac_f64_dpp %4, %4, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %10, %10, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %18 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 1 */
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %2 row_newbcast:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %5, %5, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%2, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %9, %9, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %13, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %12 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 2 */
-        "v_fmac_f64_dpp %3, %3, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %4, %4, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %3 row_newbcast:3 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%3, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %8, %8, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %12, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 3 */
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %4 row_newbcast:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%4, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %13, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %12 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 4 */
-        "v_fmac_f64_dpp %5, %5, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %5 row_newbcast:5 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%5, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %8, %8, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %12, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 5 */
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%6, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %13, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 6 */
-        "v_fmac_f64_dpp %7, %7, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %7 row_newbcast:7 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%7, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %4, %4, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %12, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %10, %10, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 7 */
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %8 row_newbcast:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%8, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %13, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 8 */
-        "v_fmac_f64_dpp %9, %9, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %10, %10, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %0, %0, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %1, %1, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%9, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %4, %4, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %12, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %6, %6, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 9 */
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %11, %11, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %0, %0, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %10 row_newbcast:10 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %1, %1, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%10, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %5, %5, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %13, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %7, %7, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 10 */
-        "v_fmac_f64_dpp %11, %11, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %0, %0, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %1, %1, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b64_dpp %14, %11 row_newbcast:11 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_fmac_f64_dpp %2, %2, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_rcp_f64 %15, %14\n\t"
-        "v_fmac_f64_dpp %3, %3, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %4, %4, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_mul_f64 %16, -%11, %15\n\t"
-        "v_fma_f64 %17, -%14, %15, 1.0\n\t"
-        "v_fmac_f64_dpp %6, %6, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fma_f64 %12, %16, %17, %16\n\t"
-        "v_fmac_f64_dpp %8, %8, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-        /* pivot 11 */
-        "v_fmac_f64_dpp %0, %0, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %1, %1, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %2, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %3, %3, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %4, %4, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %5, %5, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %6, %6, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %7, %7, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %8, %8, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %9, %9, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %10, %10, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(Mc[0]), "+v"(Mc[1]), "+v"(Mc[2]), "+v"(Mc[3]), "+v"(Mc[4]), "+v"(Mc[5]), "+v"(Mc[6]), "+v"(Mc[7]), "+v"(Mc[8]), "+v"(Mc[9]), "+v"(Mc[10]), "+v"(Mc[11]), "=&v"(qa), "=&v"(qb), "=&v"(d), "=&v"(r), "=&v"(t), "=&v"(e)
-        : "v"(nt), "v"(inv_next));
-}
-#ifdef GJ_EXEC_NOP   // (A/B: wait states after each exec write, -DGJ_EXEC_NOP=n: s_nop n)
-#define GJ_STR2(x) #x
-#define GJ_STR(x) GJ_STR2(x)
-#define GJ_EXEC_PAD "s_nop " GJ_STR(GJ_EXEC_NOP) "\n\t"
-#else
-#define GJ_EXEC_PAD ""
-#endif
 // Gauss-Jordan with one row per lane (tools/gen_gj.py solve_rows): Mc[0..11] row j of M, b
 // tau_j; returns with b the solution on lanes 2..11 (rows normalised), b * m on lanes 0 and 1
 // (scaled by 1 / m after).  f0 / f1: pivot 0 / 1's factors (-M_j0 / m0, -M_j1 / m1; 0 on lane
@@ -598,9 +374,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fmac_f64_dpp %9, %9, %22 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %10, %10, %22 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
         "v_mul_f64 %13, -%2, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %13, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 3\n\t"
         "v_fmac_f64_dpp %11, %11, %22 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %12, %12, %22 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
@@ -618,9 +394,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fmac_f64_dpp %9, %9, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %10, %10, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
         "v_mul_f64 %14, -%3, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %14, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 4\n\t"
         "v_fmac_f64_dpp %11, %11, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %12, %12, %13 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
@@ -637,9 +413,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_fmac_f64_dpp %10, %10, %14 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
         "v_mul_f64 %13, -%4, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %13, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 5\n\t"
         "v_fmac_f64_dpp %11, %11, %14 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %12, %12, %14 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
@@ -655,9 +431,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fmac_f64_dpp %10, %10, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %14, -%5, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %14, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 6\n\t"
         "v_fmac_f64_dpp %11, %11, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %12, %12, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
@@ -673,9 +449,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fmac_f64_dpp %11, %11, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %13, -%6, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %13, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 7\n\t"
         "v_fmac_f64_dpp %12, %12, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
         /* pivot 6 */
@@ -690,9 +466,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fmac_f64_dpp %12, %12, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %14, -%7, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %14, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 8\n\t"
         /* pivot 7 */
         "v_fmac_f64_dpp %8, %8, %14 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
@@ -705,9 +481,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fma_f64 %17, -%15, %16, 1.0\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %13, -%8, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %13, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 9\n\t"
         /* pivot 8 */
         "v_fmac_f64_dpp %9, %9, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
@@ -720,9 +496,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fma_f64 %17, -%15, %16, 1.0\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %14, -%9, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %14, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 10\n\t"
         /* pivot 9 */
         "v_fmac_f64_dpp %10, %10, %14 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
@@ -734,9 +510,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fma_f64 %17, -%15, %16, 1.0\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %13, -%10, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %13, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         "s_lshl_b64 %20, %23, 11\n\t"
         /* pivot 10 */
         "v_fmac_f64_dpp %11, %11, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
@@ -748,9 +524,9 @@ __device__ __forceinline__ void gj_rows(double *Mc, double &b, double f0, double
         "v_fma_f64 %17, -%15, %16, 1.0\n\t"
         "v_fma_f64 %18, %16, %17, %16\n\t"
         "v_mul_f64 %14, -%11, %18\n\t"
-        "s_and_b64 exec, %19, %20\n\t" GJ_EXEC_PAD
+        "s_and_b64 exec, %19, %20\n\t"
         "v_add_f64 %14, %18, -1.0\n\t"
-        "s_mov_b64 exec, %19\n\t" GJ_EXEC_PAD
+        "s_mov_b64 exec, %19\n\t"
         /* pivot 11 */
         "s_nop 0\n\t"
         "v_fmac_f64_dpp %12, %12, %14 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
@@ -965,7 +741,6 @@ struct LaneConst {
     double ancd[10];   // the same as 1.0 / 0.0 (rows 3 and 7 unused: bank masks): column_dots' entries are finite, so a product masks
     double cmask[9];   // composite_scan: 1.0 when body j is the parent of step s's child (edges 11-9, 10-9, 9-8, .., 3-2)
     double mc;      // the mass of body j's subtree (composite inertia's mass, a constant)
-    double inv_m0, inv_m1;   // 1 / composite mass of bodies 0 and 1: the base pivots (uniform)
     double f0, f1;  // gj_rows: pivot 0 / 1's factor per unit of M_j0 / M_j1 (-1 / m; 0 on lane 0 / 1)
     double qs;      // gj_rows: the solution's scale (1 / m on lanes 0 and 1, else 1)
 };
@@ -1337,10 +1112,7 @@ __device__ __forceinline__ void composite_scan(double *v, const double *m)
 __device__ __forceinline__ double base_velocity(const LaneConst &L, double u, double sq, double cq, double qd)
 {
     double P = 0.0, Q = 0.0, X, Y;
-    asm(
-#ifdef REGTAB
-        "s_nop 1\n\t"
-#endif
+    asm("s_nop 1\n\t"   // the operands may be written right before the block
         "v_fmac_f64_dpp %0, %5, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"    // P = c A
         "v_fmac_f64_dpp %1, %5, %9 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"    // Q = c B
         "v_mul_f64 %2, %11, %6\n\t"                                                  // X = C u
@@ -1356,7 +1128,7 @@ __device__ __forceinline__ double base_velocity(const LaneConst &L, double u, do
 }
 
 // Mass-matrix solve for the rollouts without the energy tank: qdd = M(q)^-1 tau_u, M by the
-// composite-rigid-body algorithm in world coordinates and eliminated by Gauss-Jordan, one column
+// composite-rigid-body algorithm in world coordinates and eliminated by Gauss-Jordan, one row
 // per lane.  Equal to the zero-bias articulated-body pass in exact arithmetic; its serial chain is
 // twelve scalar pivots (the pivot d_k is already on lane k) instead of twelve 6x6 levels whose
 // D = S^T A S needs a six-deep cross-lane chain each.
@@ -1364,9 +1136,9 @@ __device__ __forceinline__ double base_velocity(const LaneConst &L, double u, do
 //                       0..11 (row_shl 1, 2, 4, 8); finger 10's subtree is itself.
 //   column j            M_ij = S_i . Ic_j S_j for the ancestors i of j (S_i broadcast from lane i),
 //                       M_jj on the diagonal; the entries below the diagonal by symmetry through
-//                       LDS.  Lane 12 holds the right-hand side tau.
-//   Gauss-Jordan        twelve pivots, each one broadcast of the pivot, a reciprocal and eleven
-//                       broadcast FMAs per lane; then qdd_j = tau'_j / M'_jj.
+//                       LDS.  M is symmetric, so lane j's column is its row.
+//   Gauss-Jordan        gj_rows: lane j holds row j and its own right-hand side tau_j; twelve
+//                       pivots over the columns not yet eliminated, rows normalised as they go.
 __device__ __forceinline__ double coop_solve(int j, const LaneConst &L, const CoopBody &bd, double tau_l, double *Lk)
 {
     // (h, Ib) summed over the subtree; the subtree's mass is a per-lane constant of the body table (T_MC)
@@ -1397,42 +1169,24 @@ __device__ __forceinline__ double coop_solve(int j, const LaneConst &L, const Co
     for (int i = 0; i < 10; i++)
         if (i != 3 && i != 7) Mc[i] *= L.ancd[i];
     Mc[11] = 0.0;
-    // row j of the block: that column, then tau_j and zeros in slots 12..15, then the diagonal over
-    // slot j (LDS stores of a wave land in order).  Entry (i, j) of the block is then column i's
-    // row-j entry: M_ji = M_ij below the diagonal, the diagonal, and zero above it - so column j is
-    // its strictly-upper part plus a read of block column j, with no select; lane 12 reads the
-    // right-hand side tau, lanes 13..15 zeros.
+    // row j of the block: that column (slots 12..15 hold zeros for good, coop_rows' entry), then the
+    // diagonal over slot j (LDS stores of a wave land in order).  Entry (i, j) of the block is then
+    // column i's row-j entry: M_ji = M_ij below the diagonal, the diagonal, and zero above it - so
+    // column j is its strictly-upper part plus a read of block column j, with no select; lanes
+    // 12..15 read zeros.
     double *Row = Lk + L_COL + j * CSTR;
 #pragma unroll
     for (int i = 0; i < 12; i += 2) *reinterpret_cast<double2 *>(Row + i) = double2{Mc[i], Mc[i + 1]};
-#ifdef GJ_COLS
-    Row[12] = tau_l;   // (slots 13..15: zeros for good, coop_rows' entry)
-#endif
     Row[j] = diag;
 #pragma unroll
     for (int i = 0; i < 12; i++) Mc[i] += Lk[L_COL + i * CSTR + j];
 #pragma unroll
     for (int i = 0; i < 12; i++) PMARK_D(6, Mc[i]);
-#ifndef GJ_COLS
     // one row per lane (M symmetric: the column is the row), tau_j the lane's own right-hand side;
     // lanes 12..15 read zeros (slots 12..15 of every block row) and have tau 0, so their b stays 0
     double b = tau_l;
     gj_rows(Mc, b, Mc[0] * L.f0, Mc[1] * L.f1);
     return b * L.qs;   // rows 2..11 normalised; rows 0 and 1 times 1 / m
-#else
-    double nt = -Mc[0] * L.inv_m0;   // each pivot's block returns the next pivot's quotient
-    gj_solve(Mc, nt, L.inv_m1);
-    // The matrix is now diagonal (every row scaled alike): qdd_j = tau'_j / M'_jj.  Lane 12 leaves
-    // tau' at L_TP and every other lane its column in its own block row (read above, dead now), so
-    // lane j reads M'_jj back at slot j of that row: no per-lane register select, no branch.
-    double *dst = (j == 12) ? Lk + L_TP : Row;
-#pragma unroll
-    for (int i = 0; i < 12; i += 2) *reinterpret_cast<double2 *>(dst + i) = double2{Mc[i], Mc[i + 1]};
-    // Lanes 12..15 read 0 / 1 (L_TP + 12, 13, coop_rows' entry): qdd = 0, q = qd = 0 for good
-    const double tp = Lk[j < FR_NB ? L_TP + j : L_TP + 12];
-    const double dj = Lk[j < FR_NB ? L_COL + j * CSTR + j : L_TP + 13];
-    return tp * frcp(dj);
-#endif
 }
 
 }  // namespace
@@ -1709,11 +1463,11 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
         }
     }
     L.mc = M[T_MC];
-    L.inv_m0 = 1.0 / Lmodel[0 * MB + T_MC];   // the base pivots' constant diagonals (gj_pivot_0 / 1)
-    L.inv_m1 = 1.0 / Lmodel[1 * MB + T_MC];
     {
-        double f0 = j == 0 ? 0.0 : -L.inv_m0, f1 = j == 1 ? 0.0 : -L.inv_m1;
-        double qs = j == 0 ? L.inv_m0 : (j == 1 ? L.inv_m1 : 1.0);
+        // 1 / composite mass of bodies 0 and 1: the base pivots' constant diagonals (gj_rows)
+        const double inv_m0 = 1.0 / Lmodel[0 * MB + T_MC], inv_m1 = 1.0 / Lmodel[1 * MB + T_MC];
+        double f0 = j == 0 ? 0.0 : -inv_m0, f1 = j == 1 ? 0.0 : -inv_m1;
+        double qs = j == 0 ? inv_m0 : (j == 1 ? inv_m1 : 1.0);
         asm volatile("" : "+v"(f0), "+v"(f1), "+v"(qs));   // kept in registers across the loop
         L.f0 = f0;
         L.f1 = f1;
@@ -1791,50 +1545,39 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
         E = EN ? (FROW && frow ? fE : lE) : 0.0;   // EnergyTank::set_energy(state.available_energy)
     }
     const double *grav = a.model->gravity;
-    // REGTAB: the body-table fields the step reads, held in registers across the loop instead of
-    // re-read from LDS every step (A/B: the loop's VGPR budget against sixteen ds_read2 per step)
-    // the fields in REGTAB_MASK (bit n: field n) are loaded once, opaque, and stay in registers; the
-    // step's other fields are re-read from LDS in every step (tab_refresh).  Not in the energy-tank
-    // kernels, whose registers are spent already (their spills went 13 -> 33 with it).
-#ifdef REGTAB
-#ifndef REGTAB_MASK
-#define REGTAB_MASK 0xFFFFFFFFFFFFull
-#endif
+    // The body-table fields the step reads (bit n of RT_USED: field n) are loaded once, opaque, and
+    // stay in registers across the loop instead of being re-read from LDS in every step (round 6:
+    // 789 -> 766 instructions per step, sixteen ds_read2 fewer).  Not in the energy-tank kernels,
+    // whose registers are spent already (their spills went 13 -> 33 with it).
     constexpr bool RT = !EN;
-#else
-#define REGTAB_MASK 0ull
-    constexpr bool RT = false;
-#endif
-    constexpr uint64_t RT_USED = 0x1401FFFFFEDBull;   // fields the step reads (T_R cols 0, 1 .. T_NROT, T_FIX, T_IL)
+    constexpr uint64_t RT_USED = 0x1401FFFFFEDBull;   // T_R cols 0, 1 .. T_NROT, T_FIX, T_IL
     double Mreg[T_IL + 1];
     if constexpr (RT) {
 #pragma unroll
         for (int n = 0; n <= T_IL; n++) {
-            if ((RT_USED >> n) & (REGTAB_MASK >> n) & 1) {
+            if ((RT_USED >> n) & 1) {
                 double v = M[n];
                 asm volatile("" : "+v"(v));
                 Mreg[n] = v;
             }
         }
     }
-    auto tab_refresh = [&]() {
-        if constexpr (RT) {
-#pragma unroll
-            for (int n = 0; n <= T_IL; n++)
-                if (((RT_USED >> n) & 1) && !((REGTAB_MASK >> n) & 1)) Mreg[n] = M[n];
-        }
-    };
     const double *Mk = RT ? Mreg : M;
     double sq, cq;
     const SinCosK scK = sincos_constants();
     fsincos(q, &sq, &cq, scK);   // one sincos per lane and step: FK and base yaw
     CoopKin kin;
     CoopBody bd;
-    // coop_solve's block rows: slots 13..15 hold zeros for good (slot 12 is tau, rewritten per step)
+    // coop_solve's block rows: slots 12..15 hold zeros for good (gj_rows' dummy lanes read them)
     if constexpr (!EN) {
-        *reinterpret_cast<double2 *>(Lk + L_COL + j * CSTR + 12) = double2{0.0, 0.0};   // (12: tau with GJ_COLS)
+        *reinterpret_cast<double2 *>(Lk + L_COL + j * CSTR + 12) = double2{0.0, 0.0};
         *reinterpret_cast<double2 *>(Lk + L_COL + j * CSTR + 14) = double2{0.0, 0.0};
-        *reinterpret_cast<double2 *>(Lk + L_TP + 12) = double2{0.0, 1.0};   // coop_solve's dummy-lane reads
+        // nothing reads this one (the column solve's dummy lanes did; the two doubles past the
+        // block lie in L_S, which only the tank's pass uses).  It stays because the step loops'
+        // register allocation hangs on it: without it, wherever the zeroing above is placed, the
+        // compact one-wave and four-wave loops grow from 803 to 836-859 instructions with a scratch
+        // reload per step (tools/loop_count.py).  Drop it with the next change to the step.
+        *reinterpret_cast<double2 *>(Lk + L_COL + 16 * CSTR + 12) = double2{0.0, 1.0};
     }
     if (kb == 0) {
         coop_fk<CK, false>(L, q, sq, cq, qd, M, Lk, kin, bd, grav);   // set_state -> calculate() at (q0, v0)
@@ -1861,7 +1604,6 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
         qd = base_velocity(L, u, sq, cq, qd);
         if constexpr (EN)
             Lw[L_TAU + j] = (j >= 3 && j < 10) ? u : 0.0;   // coop_aba's tau
-        tab_refresh();
         coop_fk<CK, EN>(L, q, sq, cq, qd, Mk, Lk, kin, bd, grav);
         // the next record's kinematics (the one-step lag)
         if constexpr (KC) store_ks<CK, EN>(recp(k + 1), j, L, bd, qd, Lk);
@@ -2032,8 +1774,6 @@ __device__ __forceinline__ bool row_live(const FrRolloutArgs &a, int64_t lr)
 // (p >= last + 3), and the last chunk after the wave's loop (its flag, behind s_waitcnt 0).  Chunks
 // of CH = 16 records are whole 128-byte lines (16 x 336 B = 42 lines, rows 21504 B apart), so no
 // line a chunk reads is written after it.  The relay's rows are taken after their last stage.
-constexpr int CH = 16;          // steps per chunk
-constexpr int HC_MAX = 128;     // the horizon bound of the objective in this launch (Lcs)
 // LDS words (Lq): the main waves' steps, the groups' next chunk to take and chunks completed, the
 // relay's stage
 enum { Q_PROG = 0, Q_NEXT = 4, Q_DONE = 9, Q_STAGE = 14, Q_N = 16 };
@@ -2108,10 +1848,7 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
     const StepConst *stp = frow ? a.fsteps : a.steps;
     const int kk = live ? k : 0;
     PMARK(8);
-#ifndef COST_JG
-#define COST_JG 2
-#endif
-    double cs = mppi_cost::record_step_cost<CK, EN, MB, false, COST_JG>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO);
+    double cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO);
     PMARK_D(9, cs);
     if (live) Lcs[(g * ROWS_PER_WAVE + i) * HC_MAX + k] = cs;
     // the stores before the count: the wave that completes the group reads every chunk's costs
@@ -2399,7 +2136,7 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // on the free CU (per-block traces, tools/wave_trace.py).
 // KC: compact records with the kinematic sums on the rows' chains (the update's launches, throughput-
 // bound); the standalone filter() row (one latency-bound row) keeps the 768-B record and a shorter step.
-template <int CK, bool EN, int WPB, bool FROW, bool KC>
+template <int CK, bool EN, int WPB, bool KC>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_kernel(FrRolloutArgs a)
 {
     constexpr int KS = EN ? LDS_KIN_EN : LDS_KIN;
@@ -2424,8 +2161,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
             kept_rows_wave(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, rk);
         }
     }
-    coop_rows<CK, EN, FROW, 0, false, KC>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, lds_kin + wrow * KS,
-                                          lds_scr + wrow * LDS_SCR, Lmodel, Lx0);
+    coop_rows<CK, EN, false, 0, false, KC>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, lds_kin + wrow * KS,
+                                           lds_scr + wrow * LDS_SCR, Lmodel, Lx0);
     if constexpr (WPB == 4) {
         if (a.costs_in_launch) launch_costs<CK, EN, KC>(a, wv, lane, Lmodel);
     } else if constexpr (WPB == 1) {
@@ -2523,10 +2260,6 @@ __global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
 namespace mppi_eng {
 
-// The device's CU count is the handle's (EnvSwitches::cus, hipDeviceAttributeMultiprocessorCount
-// at create): one round of workgroups is one per CU
-static int64_t cu_count(const EnvSwitches &env) { return env.cus ? (int64_t)env.cus : 256; }
-
 // Dynamic LDS that lifts a multi-wave workgroup above half of the CU's 160 KiB, so that the
 // dispatcher places one workgroup per CU (one wave per SIMD) whatever the kernel's static LDS
 // (which the compiler trims per variant): two workgroups on a CU would double up its SIMDs.
@@ -2540,11 +2273,11 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
     return at.sharedSizeBytes >= want ? 0u : (unsigned)(want - at.sharedSizeBytes);
 }
 
-template <int CK, bool EN, int WPB, bool FROW, bool KC>
+template <int CK, bool EN, int WPB, bool KC>
 static void launch_k(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-    static const unsigned pad = one_per_cu_pad(fr_coop_kernel<CK, EN, WPB, FROW, KC>, WPB);
-    hipLaunchKernelGGL((fr_coop_kernel<CK, EN, WPB, FROW, KC>), dim3(nb), dim3(64 * WPB), pad, s, a);
+    static const unsigned pad = one_per_cu_pad(fr_coop_kernel<CK, EN, WPB, KC>, WPB);
+    hipLaunchKernelGGL((fr_coop_kernel<CK, EN, WPB, KC>), dim3(nb), dim3(64 * WPB), pad, s, a);
 }
 
 template <int CK, bool EN>
@@ -2554,12 +2287,12 @@ static void launch_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
     hipLaunchKernelGGL((fr_coop_x_kernel<CK, EN>), dim3(nb), dim3(64 * XW), pad, s, a);
 }
 
-template <int WPB, bool FROW, bool KC>
+template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-    if (a.cost_kind == CK_TRACK_POINT) launch_k<CK_TRACK_POINT, false, WPB, FROW, KC>(a, nb, s);
-    else if (a.energy) launch_k<CK_ASSISTED_MANIPULATION, true, WPB, FROW, KC>(a, nb, s);
-    else launch_k<CK_ASSISTED_MANIPULATION, false, WPB, FROW, KC>(a, nb, s);
+    if (a.cost_kind == CK_TRACK_POINT) launch_k<CK_TRACK_POINT, false, WPB, KC>(a, nb, s);
+    else if (a.energy) launch_k<CK_ASSISTED_MANIPULATION, true, WPB, KC>(a, nb, s);
+    else launch_k<CK_ASSISTED_MANIPULATION, false, WPB, KC>(a, nb, s);
 }
 
 bool fr_coop_compact(const FrRolloutArgs &a) { return !a.optimal; }
@@ -2568,8 +2301,8 @@ hipError_t launch_fr_coop(const FrRolloutArgs &a, hipStream_t s)
 {
     const unsigned nb = (unsigned)((a.count + ROWS_PER_WAVE - 1) / ROWS_PER_WAVE);
     if (nb == 0) return hipSuccess;
-    if (fr_coop_compact(a)) launch_one<1, false, true>(a, nb, s);
-    else launch_one<1, false, false>(a, nb, s);   // the standalone filter() row
+    if (fr_coop_compact(a)) launch_one<1, true>(a, nb, s);
+    else launch_one<1, false>(a, nb, s);   // the standalone filter() row
     return hipGetLastError();
 }
 
@@ -2582,42 +2315,8 @@ hipError_t launch_fr_body_table(const DevModel *model, const DevCost *cost, doub
 // The A/B switches (EnvSwitches, the handle's copy): MPPI_COSTS_IN_LAUNCH=0 keeps the separate
 // fr_step_cost_kernel; MPPI_HANDOVER=0 leaves the rows left over on wave 4 for the whole horizon,
 // beside main wave 0, instead of the relay; MPPI_SPLIT=0 runs rows just past two waves per SIMD as
-// one-wave workgroups.
+// one-wave workgroups (coop_plan.hpp).
 bool fr_coop_costs_in_launch(const EnvSwitches &env) { return !env.costs_in_launch_off; }
-
-// Whether `count` rows run as two fr_coop_x_kernel launches (launch_fr_coop_update): one-wave
-// workgroups hold two waves per SIMD, 32 rows per CU and round (8192 on 256 CUs), and a count just
-// past that - R = S + 2 at S = 8192, configs[4]'s share per GPU - leaves one wave for a second
-// round that runs alone for the whole horizon (1.49 + 1 lone-wave horizons, plus the separate cost
-// kernel).  Two launches of one wave per SIMD (each 1.06-1.1 lone-wave horizons with the objective
-// beside the loops) take less: the first over one round of full four-wave groups, the second over
-// the rest, whose rows left over and the folded filter() row travel through its relay.
-bool fr_coop_update_split(int64_t count, const EnvSwitches &env)
-{
-    constexpr int64_t WG_ROWS = 4 * ROWS_PER_WAVE;
-    const int64_t round = cu_count(env) * WG_ROWS;
-    if (count <= 2 * round || env.split_off) return false;
-    const int64_t rest = count - round, gb = rest / WG_ROWS, xb = rest - gb * WG_ROWS + 1;   // + a folded filter() row
-    return gb > 0 && gb <= cu_count(env) && xb <= gb * ROWS_PER_WAVE;
-}
-
-// Whether launch_fr_coop_update runs rounds of four-wave groups (the launches that can sample
-// their kept rows, a.drawn_ahead) for `count` rows: one round, or the two launches of the split.
-bool fr_coop_update_fusable(int64_t count, const EnvSwitches &env)
-{
-    constexpr int64_t WG_ROWS = 4 * ROWS_PER_WAVE;
-    const int64_t groups = count / WG_ROWS, xrows = count - groups * WG_ROWS + 1;   // + a folded filter() row
-    return (groups > 0 && groups <= cu_count(env) && xrows <= groups * ROWS_PER_WAVE) || fr_coop_update_split(count, env);
-}
-
-bool fr_coop_update_folds(int64_t count, int H, const EnvSwitches &env)
-{
-    if (env.costs_in_launch_off || H > HC_MAX) return false;
-    if (fr_coop_update_split(count, env)) return true;
-    constexpr int64_t WG_ROWS = 4 * ROWS_PER_WAVE;
-    const int64_t groups = count / WG_ROWS, extra = count - groups * WG_ROWS;
-    return extra > 0 && groups > 0 && groups <= cu_count(env) && extra + 1 <= groups * ROWS_PER_WAVE;
-}
 
 bool fr_coop_is_update_kernel(const void *f)
 {
@@ -2651,114 +2350,35 @@ static FrRolloutArgs row_slice(const FrRolloutArgs &a, int64_t r0, int64_t n)
     return b;
 }
 
-// Relay members for a launch of `groups` workgroups with xrows rows left over (a.relay_k): the
-// engine's exchange buffer (a.rx), the hand-over, a member workgroup q + RELAY_STRIDE m in the grid for
-// every relay group q, at least one chunk and four steps per member; else one workgroup.  Two by
-// default: at 4096 x 64 (profiles/r06/relay_k) K = 2 ran 0.1838-0.1848 ms/update against 0.1881-0.1892
-// for K = 1, 0.1858-0.1880 for K = 3 and 0.1871-0.1879 for K = 4 (each member's first stage pays
-// ~10 us of hand-over and its own setup, so more members stop paying off past two); with gj_rows
-// K = 2 0.1757-0.1772, K = 1 0.1789-0.1823, K = 3 0.1776-0.1791 (ab_gjrows.txt).
-constexpr int RELAY_K_DEFAULT = 2;
-static int relay_members(const FrRolloutArgs &a, int64_t groups, int64_t xrows, const EnvSwitches &env)
+// The arguments of launch i of the plan (coop_plan.hpp) from the update's: what the launch passes
+// and what the hipGraph path writes into its rollout nodes
+FrRolloutArgs fr_coop_launch_args(const FrRolloutArgs &a0, const CoopPlan &p, int i)
 {
-    if (!a.handover || a.rx == nullptr || xrows <= 0) return 1;
-    const int64_t nxb = (xrows + ROWS_PER_WAVE - 1) / ROWS_PER_WAVE;
-    const int nch = (a.H + CH - 1) / CH;
-    int K = std::min(env.relay_k ? env.relay_k : RELAY_K_DEFAULT, RELAY_K_MAX);
-    K = std::min(K, nch);
-    if (nxb > RELAY_GROUPS_MAX) return 1;
-    for (; K > 1; K--) {
-        if (nxb + (int64_t)RELAY_STRIDE * (K - 1) > groups) continue;
-        bool ok = true;
-        for (int m = 0; m < K && ok; m++) {
-            const int k0 = m == 0 ? 0 : (m * nch / K) * CH - 1, k1 = m + 1 == K ? a.H - 1 : ((m + 1) * nch / K) * CH - 1;
-            ok = k1 - k0 >= 4;
-        }
-        if (ok) break;
-    }
-    return K;
+    const CoopLaunch &l = p.l[i];
+    FrRolloutArgs a = a0;
+    a.costs_in_launch = p.costs_in_launch ? 1 : 0;
+    a.handover = p.handover ? 1 : 0;
+    if (!p.tail_draws) a.ahead_noise = nullptr;
+    if (!p.folded || i + 1 < p.nlaunch) a.fcost = nullptr;   // the previous filter() rides with the rows left over
+    if (p.nlaunch > 1) a = row_slice(a, l.row0, l.rows);
+    a.xbase = l.xbase;
+    a.xrows = l.xrows;
+    a.relay_k = l.relay_k;
+    return a;
 }
 
-// The update's rollouts.  e0 / e1 (may be null): timing events around the rollout launch.
-hipError_t launch_fr_coop_update(const FrRolloutArgs &a0, const EnvSwitches &env, hipStream_t s, hipEvent_t e0, hipEvent_t e1, bool *folded,
-                                 bool *costs_done, bool *tail_drawn, FrRolloutArgs *final, bool *x_kernel, bool dry,
-                                 CoopTail *tail, FrRolloutArgs *final2)
+// The update's rollouts as planned.  e0 / e1 (may be null): timing events around the launches.
+hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const CoopPlan &p, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
-    *costs_done = false;
-    *tail_drawn = false;
-    if (x_kernel) *x_kernel = false;
-    if (tail) *tail = CoopTail{};
-    constexpr int64_t WG_ROWS = 4 * ROWS_PER_WAVE;
-    *folded = false;
-    if (fr_coop_update_split(a0.count, env)) {   // two launches: one round of full groups, then the rest
-        const int64_t n0 = cu_count(env) * WG_ROWS, rest = a0.count - n0;
-        FrRolloutArgs a = a0;
-        a.costs_in_launch = !env.costs_in_launch_off && a.H <= HC_MAX ? 1 : 0;
-        a.handover = env.handover_off ? 0 : 1;
-        if (!a.costs_in_launch || !a.drawn_ahead) a.ahead_noise = nullptr;
-        FrRolloutArgs A = row_slice(a, 0, n0), B = row_slice(a, n0, rest);
-        A.fcost = nullptr;   // the previous filter() rides with the rows left over
-        A.xbase = n0;
-        A.xrows = 0;
-        const int64_t gb = rest / WG_ROWS, xb = rest - gb * WG_ROWS;
-        const bool frow = a0.fcost != nullptr;
-        if (!frow) B.fcost = nullptr;
-        B.xbase = gb * WG_ROWS;
-        B.xrows = xb + (frow ? 1 : 0);
-        A.relay_k = 1;
-        B.relay_k = relay_members(B, gb, B.xrows, env);
-        *folded = frow;
-        *costs_done = a.costs_in_launch != 0;
-        *tail_drawn = a.ahead_noise != nullptr;
-        if (final) *final = A;
-        if (final2) *final2 = B;
-        if (x_kernel) *x_kernel = true;
-        if (tail) *tail = CoopTail{n0, n0 + B.xbase, (int)((B.xrows + 3) / 4), 2};
-        if (dry) return hipSuccess;
-        if (e0) (void)hipEventRecord(e0, s);
-        launch_x_any(A, (unsigned)cu_count(env), s);
-        launch_x_any(B, (unsigned)gb, s);
-        if (e1) (void)hipEventRecord(e1, s);
-        return hipGetLastError();
-    }
-    const int64_t groups = a0.count / WG_ROWS, extra = a0.count - groups * WG_ROWS;
-    // the previous update's filter() rides along when there are extra rows anyway (the fifth wave
-    // of the first workgroup has room); alone it would add a wave, so then it stays pending
-    const bool frow = a0.fcost != nullptr && extra > 0;
-    const int64_t xrows = extra + (frow ? 1 : 0);
-    FrRolloutArgs a = a0;
-    if (groups == 0 || groups > cu_count(env) || xrows > groups * ROWS_PER_WAVE) {
-        if (a.drawn_ahead) return hipErrorInvalidValue;   // the one-wave launch samples nothing
-        a.fcost = nullptr;   // more than one round of workgroups: one-wave workgroups throughout
-        a.ahead_noise = nullptr;
-        a.relay_k = 1;
-        a.costs_in_launch = groups > 0 && !env.costs_in_launch_off ? 1 : 0;   // each wave its own rows'
-        *costs_done = a.costs_in_launch != 0;
-        if (final) *final = a;
-        if (dry) return hipSuccess;
-        if (e0) (void)hipEventRecord(e0, s);
-        const hipError_t e = launch_fr_coop(a, s);
-        if (e1) (void)hipEventRecord(e1, s);
-        return e;
-    }
-    if (!frow) a.fcost = nullptr;
-    a.xbase = groups * WG_ROWS;
-    a.xrows = xrows;
-    *folded = frow;
-    a.costs_in_launch = !env.costs_in_launch_off && a.H <= HC_MAX ? 1 : 0;   // Lcs holds HC_MAX steps
-    a.handover = env.handover_off ? 0 : 1;
-    a.relay_k = relay_members(a, groups, xrows, env);
-    *costs_done = a.costs_in_launch != 0;
-    // tail draws ride in launch_costs of fr_coop_x_kernel only, and need the sampling arguments
-    if (xrows == 0 || !a.costs_in_launch || !a.drawn_ahead) a.ahead_noise = nullptr;
-    *tail_drawn = a.ahead_noise != nullptr;
-    if (final) *final = a;
-    if (x_kernel) *x_kernel = xrows != 0;
-    if (tail) *tail = CoopTail{0, a.xbase, (int)((xrows + 3) / 4), 1};
-    if (dry) return hipSuccess;
+    if (p.error) return hipErrorInvalidValue;
     if (e0) (void)hipEventRecord(e0, s);
-    if (xrows == 0) launch_one<4, false, true>(a, (unsigned)groups, s);
-    else launch_x_any(a, (unsigned)groups, s);
+    for (int i = 0; i < p.nlaunch; i++) {
+        const CoopLaunch &l = p.l[i];
+        const FrRolloutArgs b = fr_coop_launch_args(a, p, i);
+        if (l.kind == COOP_X) launch_x_any(b, l.grid, s);
+        else if (l.kind == COOP_FOUR_WAVE) launch_one<4, true>(b, l.grid, s);
+        else if (l.grid) launch_one<1, true>(b, l.grid, s);
+    }
     if (e1) (void)hipEventRecord(e1, s);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "coop_plan.hpp"
 #include "engine_types.hpp"
 #include "../../include/mppi_amd.h"
 
@@ -149,9 +150,9 @@ struct FrRolloutArgs {
     // x0 back for the kernels after it.
     int drawn_ahead;
     SampleArgs samp;
-    // costs_in_launch (set by launch_fr_coop_update): the waves evaluate the objective of the rows
-    // after their horizon loops (fr_coop.hip launch_costs) instead of fr_step_cost_kernel; stats as
-    // in FrCostArgs
+    // costs_in_launch (set by fr_coop_launch_args from the plan): the waves evaluate the objective of
+    // the rows after their horizon loops (fr_coop.hip launch_costs) instead of fr_step_cost_kernel;
+    // stats as in FrCostArgs
     int costs_in_launch;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
@@ -174,7 +175,6 @@ struct FrRolloutArgs {
     uint32_t rtoken;
     int relay_k;
 };
-constexpr int RELAY_K_MAX = 4, RELAY_STRIDE = 8, RELAY_GROUPS_MAX = 4;
 // One relay group's hand-offs between consecutive members (m -> m + 1, m < RELAY_K_MAX - 1): the
 // 64 lanes' (q, qd, E) and the four rows' partial cost sums, each behind a token on a line of its own
 struct RelayXfer {
@@ -247,10 +247,6 @@ struct PmRolloutArgs {
     int optimal;
 };
 
-
-
-
-// stable rank of rollouts 2..S+1 by cost; `sorted` is scratch of rank_scratch(S) keys
 // ---- wrench forecast on the device (forecast.hip) --------------------------------------------
 constexpr int FC_NONE = -1, FC_LOCF = 0, FC_AVERAGE = 1, FC_KALMAN = 2;   // mppi_forecast_type
 constexpr int KMAX = 24;   // Kalman states 6 (order + 1), order <= 3
@@ -330,46 +326,13 @@ hipError_t launch_fr_coop(const FrRolloutArgs &a, hipStream_t s);
 // whether launch_fr_coop writes compact records (FR_REC_C): every launch but the standalone filter()
 // row's (a.optimal), which keeps the 768-B record and the shorter step of a latency-bound row
 bool fr_coop_compact(const FrRolloutArgs &a);
-// The update's rollouts (fr_coop_x_kernel): one workgroup per CU of four one-SIMD waves of rollouts
-// plus a fifth wave for the rows left over (and, when there are some, the previous update's
-// filter() as one more row: *folded).  Falls back to launch_fr_coop beyond one round of CUs.
-// The update's rollouts (fr_coop.hip): e0 / e1 = optional timing events around the launch.
-// *tail_drawn: the launch made the next update's draws for its main waves' rows (a.ahead_noise).
-// final (may be null): the arguments the launch used; *x_kernel: it was fr_coop_x_kernel (one round
-// of four-wave workgroups with a fifth wave); dry: decide and fill them, launch nothing.
-// Rows past one round of workgroups by less than a workgroup's (fr_coop_update_split) run as two
-// launches of fr_coop_x_kernel, the first over one round of full groups (its arguments in *final),
-// the second over the rest (*final2); *tail (may be null) tells rank_draw_kernel where the second
-// launch's rows left for it are.
-struct CoopTail {
-    int64_t row0 = 0;    // first row of the launch with the rows left over
-    int64_t xbase = 0;   // the rows left over start here (launch rows)
-    int nxb = 0;         // workgroups of that launch whose first wave's rows rank_draw_kernel draws
-    int launches = 1;
-};
-struct EnvSwitches;
-hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const EnvSwitches &env, hipStream_t s, hipEvent_t e0, hipEvent_t e1, bool *folded,
-                                 bool *costs_done, bool *tail_drawn, FrRolloutArgs *final = nullptr, bool *x_kernel = nullptr,
-                                 bool dry = false, CoopTail *tail = nullptr, FrRolloutArgs *final2 = nullptr);
-bool fr_coop_update_fusable(int64_t count, const EnvSwitches &env);
-bool fr_coop_update_split(int64_t count, const EnvSwitches &env);   // the two-launch case of launch_fr_coop_update
+// The update's rollouts (fr_coop.hip) as coop_plan (coop_plan.hpp) shaped them: one launch, or the
+// split's two.  e0 / e1 = optional timing events around the launches.
+hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const CoopPlan &p, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+// The arguments launch i of the plan takes (the hipGraph path updates its rollout nodes with them)
+FrRolloutArgs fr_coop_launch_args(const FrRolloutArgs &a, const CoopPlan &p, int i);
 bool fr_coop_costs_in_launch(const EnvSwitches &env);   // the objective runs in the update launch (MPPI_COSTS_IN_LAUNCH != 0)
-// A/B switches from the environment, read once per mppi_create into the handle (tests set them
-// before creating a handle): a handle's launch paths never change under it, and no getenv runs on
-// the update path (~80 ns each)
-struct EnvSwitches {
-    bool draw_ahead_off, tail_draws_off, pm_fused_off, costs_in_launch_off, handover_off, split_off, stream_prio_off;
-    int relay_k;   // MPPI_RELAY_K: workgroups the rows left over travel through (1..RELAY_K_MAX; 0: the default)
-    // the handle's device: its CU count (the rollout launches' rounds of workgroups) and LDS per
-    // block (the fused point mass's residency check), set at create for that device - per handle, so
-    // that handles created on different devices from several threads never read each other's
-    unsigned cus;
-    int lds_max;
-};
 EnvSwitches env_switches_read();
-// Whether a pending filter() folds into the update launch of `count` rows with the objective in
-// the launch (fr_coop_x_kernel, one launch or the split's two): the hipGraph path's launch shape
-bool fr_coop_update_folds(int64_t count, int H, const EnvSwitches &env);
 constexpr int FR_BODY_TABLE = 13 * 46;   // doubles of the cooperative kernels' body table (>= LDS_MODEL)
 hipError_t launch_fr_body_table(const DevModel *model, const DevCost *cost, double *table, hipStream_t s);
 hipError_t launch_finish(const FinishArgs &a, hipStream_t s);

@@ -3,7 +3,7 @@ set -e
 cd "$(dirname "$0")"
 python3 - <<'PY'
 s = open("../../assistedmanipulation_amd/csrc/fr_coop.hip").read()
-a = s.index("#ifdef GJ_EXEC_NOP")
+a = s.index("// Gauss-Jordan with one row per lane")
 b = s.index("\n}\n", s.index("void gj_rows")) + 3
 open("gj_rows_gen.inc", "w").write(s[a:b])
 PY
