@@ -62,16 +62,23 @@ struct CoopPlan {
     bool folded;         // the pending filter() rides as one more row of the last launch
     bool costs_in_launch;   // the launch evaluates the objective: no fr_step_cost_kernel after it
     bool tail_draws;     // the launch makes the next update's draws for its main waves' rows
-    bool handover;       // the rows left over travel through relay stages (MPPI_HANDOVER=0: one wave beside main wave 0)
+    bool handover;       // the rows left over travel through relay stages (MPPI_HANDOVER=0, H < 5: one wave beside main wave 0)
     CoopTail tail;
 };
+
+// The rows left over travel through relay stages: four stages of a member share its loop steps,
+// stage r from step (r (H - 1)) / 4, and a stage that starts at step 0 does not wait for the stage
+// before it.  With fewer than four loop steps two stages would start at 0 and store the hand-over
+// state and the stage word unordered, so such a horizon keeps the rows on one wave (the members'
+// four-step rule below, for the one-member relay).
+inline bool coop_handover(int H, const EnvSwitches &env) { return !env.handover_off && H - 1 >= 4; }
 
 // Relay members for a launch of `groups` workgroups with xrows rows left over: needs the engine's
 // exchange buffer, the hand-over, a member workgroup q + RELAY_STRIDE m in the grid for every relay
 // group q, and at least one chunk and four steps per member; else one workgroup.
 inline int coop_relay_members(int H, int64_t groups, int64_t xrows, bool relay_buffer, const EnvSwitches &env)
 {
-    if (env.handover_off || !relay_buffer || xrows <= 0) return 1;
+    if (!coop_handover(H, env) || !relay_buffer || xrows <= 0) return 1;
     const int64_t nxb = (xrows + ROWS_PER_WAVE - 1) / ROWS_PER_WAVE;
     const int nch = (H + CH - 1) / CH;
     int K = env.relay_k ? env.relay_k : RELAY_K_DEFAULT;
@@ -124,7 +131,7 @@ inline CoopPlan coop_plan(int64_t count, int H, bool filter_pending, bool drawn_
                               coop_relay_members(H, groups, xrows, relay_buffer, env)};
         p.folded = frow;
         p.costs_in_launch = x_costs;
-        p.handover = !env.handover_off;
+        p.handover = coop_handover(H, env);
         p.tail_draws = p.x_kernel && x_costs && drawn_ahead && tail_buffer;
         p.tail = {row0, row0 + groups * WG_ROWS, (int)((xrows + 3) / 4), p.nlaunch};
     };

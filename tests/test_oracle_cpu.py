@@ -211,6 +211,37 @@ def test_operation_orders_delta(model, self_collision):
             assert np.nanmin(a.costs()) < 1e6
 
 
+def test_operation_orders_delta_small_track_point():
+    """The scale of test_gpu_launch_shapes.LOOSER's host-noise bar: the oracle's two fp64 operation
+    orders on that test's own stream (145 rollouts x 33 steps, TrackPoint with every term, seed 3)
+    differ by 1.09e-11 relative, above helpers.COST_RTOL by themselves; the bar keeps two to three
+    orders over the measured gap.  (The other two LOOSER cases replay the device's Philox draws,
+    which no CPU test has; their gaps were measured on the GPU box and stand beside their bars.)"""
+    from helpers import cost_errors
+    from launch_shapes import by_name, horizon
+    from test_gpu_launch_shapes import LOOSER, TIMES, _track_point_all_terms
+    name, S, H, keep = by_name("r147_h33")[:4]
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    cc, keepalive = conf.to_c()
+    d, c = am.FrankaRidgebackDynamics().descriptor(), _track_point_all_terms().descriptor()
+    a, b = (O.OracleTrajectory(cc, d, c, scalar=0, mode=m) for m in (0, 1))
+    for t in (a, b):
+        t.set_forecast(am.constant_forecast(t.H))
+    rng = np.random.default_rng(3)
+    sd = np.sqrt(np.diag(conf.covariance))
+    x = am.huddled_state()
+    gap = 0.0
+    for time in TIMES:
+        eps = rng.standard_normal((a.noise_draws(time), 12)) * sd
+        for t in (a, b):
+            t.inject_noise(eps)
+            t.update(x, time)
+        gap = max(gap, cost_errors(b.costs(), a.costs(), a.H)[0])
+    bar = LOOSER[("host", name, "track_point")]["cost_rtol"]
+    print("oracle orders: %.3e relative" % gap)
+    assert bar / 1000 <= gap <= bar / 10, gap
+
+
 def test_end_effector_orientation_and_acceleration(model):
     """The EndEffectorState members DynamicsForecast records beyond kinematics.npz (dynamics.cpp:
     115-116): the EE orientation and its WORLD spatial acceleration (Pinocchio's forward pass,
