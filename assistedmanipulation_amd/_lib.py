@@ -85,6 +85,11 @@ PROTOTYPES = {
     "mppi_dynamics_query": (C.c_int, [_h, _dp]),
     "mppi_dynamics_forecast": (C.c_int, [_h, _dp, C.c_double, C.c_double, C.c_int64, _dp, _dp]),
     "mppi_cost_evaluate": (C.c_int, [C.POINTER(abi.mppi_cost_desc), _h, _dp, _dp, _dp, _dp]),
+    "mppi_link_name": (C.c_char_p, [C.c_int]),
+    "mppi_set_link_positions": (C.c_int, [_h, C.c_int]),
+    "mppi_get_link_positions": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_dynamics_set_link_positions": (C.c_int, [_h, C.c_int]),
+    "mppi_dynamics_link_positions": (C.c_int, [_h, _dp]),
 }
 
 _lib = None

@@ -50,6 +50,15 @@ MPPI_DF_JOINT_POSITION, MPPI_DF_END_EFFECTOR = 0, 12
 MPPI_DF_JOINT_POWER, MPPI_DF_EXTERNAL_POWER, MPPI_DF_ENERGY, MPPI_DF_WRENCH = 112, 113, 114, 115
 MPPI_DF_N = 121
 MPPI_DYNAMICS_QUERY_N = 54
+# FrankaRidgeback::Link (MPPI_LINK_*), the reference's LINK_NAMES, and the link-position models
+(MPPI_LINK_OMNI_BASE_ROOT_LINK, MPPI_LINK_X_SLIDER, MPPI_LINK_Y_SLIDER, MPPI_LINK_PIVOT, MPPI_LINK_PANDA_LINK1,
+ MPPI_LINK_PANDA_LINK2, MPPI_LINK_PANDA_LINK3, MPPI_LINK_PANDA_LINK4, MPPI_LINK_PANDA_LINK5, MPPI_LINK_PANDA_LINK6,
+ MPPI_LINK_PANDA_LINK7, MPPI_LINK_PANDA_LEFTFINGER, MPPI_LINK_PANDA_RIGHTFINGER) = range(13)
+MPPI_LINK_N = 13
+LINK_NAMES = ("omni_base_root_link", "x_slider", "y_slider", "pivot", "panda_link1", "panda_link2", "panda_link3",
+              "panda_link4", "panda_link5", "panda_link6", "panda_link7", "panda_leftfinger", "panda_rightfinger")
+MPPI_LINK_POSITIONS_ZERO = 0
+MPPI_LINK_POSITIONS_KINEMATIC = 1
 TERM_NAMES = ("joint_limit", "self_collision", "workspace", "energy_tank", "joint_velocity", "trajectory",
               "manipulability")
 

@@ -53,6 +53,22 @@ namespace {
 
 std::string g_last_error;
 
+// MPPI_LINK_POSITIONS: the link-position model new handles and dynamics objects start in.  Unset:
+// the zero stub.  The whole string must be "0" or "1"; false with a message otherwise.
+bool env_link_positions(int &mode, std::string &why)
+{
+    mode = MPPI_LINK_POSITIONS_ZERO;
+    const char *e = std::getenv("MPPI_LINK_POSITIONS");
+    if (!e) return true;
+    if (e[0] == '0' && e[1] == '\0') return true;
+    if (e[0] == '1' && e[1] == '\0') {
+        mode = MPPI_LINK_POSITIONS_KINEMATIC;
+        return true;
+    }
+    why = std::string("MPPI_LINK_POSITIONS must be 0 or 1, not \"") + e + "\"";
+    return false;
+}
+
 struct DeviceBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -101,6 +117,9 @@ struct mppi_handle {
     double ht_sum[3] = {0, 0, 0};
     int64_t ht_n[3] = {0, 0, 0};
     int dyn_kind = 0, cost_kind = 0;
+    // mppi_set_link_positions: MPPI_LINK_POSITIONS_ZERO (the reference's stub) or _KINEMATIC; fixed
+    // once the first update has run (the launch plan and a captured graph hold its kernels)
+    int link_positions = MPPI_LINK_POSITIONS_ZERO;
     int64_t S = 0, K = 0, R = 0, H = 0, C = 0, X = 0;
     double dt = 0, gradient_step = 0, cost_scale = 0, gamma = 1;
     int control_bound = 0;
@@ -435,6 +454,8 @@ void build_dev_cost(const mppi_cost_desc &cost, DevCost &c)
             sc += left_barrier_h(t.self_collision_limit, radii - distance);
         }
         c.tp_self = sc;
+        c.sc_limit = devb(t.self_collision_limit);
+        for (int i = 0; i < SC_LINKS; i++) c.sc_radii[i] = t.self_collision_radii[i];
         c.tp_reach = devb(t.maximum_reach_limit);
     } else {
         c.en_joint = a.enable_joint_limit;
@@ -459,6 +480,8 @@ void build_dev_cost(const mppi_cost_desc &cost, DevCost &c)
             sc += left_barrier_h(a.self_collision_limit, distance - radii);
         }
         c.self_collision = sc;
+        c.sc_limit = devb(a.self_collision_limit);
+        for (int i = 0; i < SC_LINKS; i++) c.sc_radii[i] = a.self_collision_radii[i];
         c.ws_above = devb(a.workspace_limit_above);
         c.ws_infront = devb(a.workspace_limit_infront);
         c.ws_reach = devb(a.workspace_limit_reach);
@@ -584,6 +607,7 @@ struct mppi_dynamics {
     double *d_buf = nullptr;   // forecast rows / cost output / wrench rows
     size_t buf_doubles = 0;
     DevPinocchio *h_obj = nullptr;   // pinned host copy for the queries
+    int link_positions = MPPI_LINK_POSITIONS_ZERO;   // mppi_dynamics_set_link_positions
     std::string err;
 };
 
@@ -666,8 +690,11 @@ mppi_status mppi_dynamics_create(const mppi_dynamics_desc *desc, const double *i
         return dfail(nullptr, MPPI_ERR_UNSUPPORTED, "the dynamics object is FrankaRidgeback::PinocchioDynamics only");
     std::string why;
     if (check_topology(desc->frankaridgeback, why) != MPPI_OK) return dfail(nullptr, MPPI_ERR_UNSUPPORTED, why);
+    int link_mode = 0;
+    if (!env_link_positions(link_mode, why)) return dfail(nullptr, MPPI_ERR_INVALID, why);
     d = new mppi_dynamics();
     d->device = device;
+    d->link_positions = link_mode;
     auto bail = [&](mppi_status st) {
         std::string m = d->err;
         mppi_dynamics_destroy(d);
@@ -815,11 +842,43 @@ mppi_status mppi_cost_evaluate(const mppi_cost_desc *cost, mppi_dynamics *d, con
     const double zero[3] = {0, 0, 0};
     a.sc = step_const(cost->assisted_manipulation, wrench6 ? wrench6 : zero, wrench6 != nullptr, 1.0);
     a.out = d->d_buf;
+    a.link_positions = d->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
     st = obj_run(d, a);
     if (st != MPPI_OK) return st;
     DHIP_TRY(hipMemcpyAsync(out8, d->d_buf, 8 * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     DHIP_TRY(hipStreamSynchronize(d->stream));
     return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_set_link_positions(mppi_dynamics *d, int mode)
+{
+    if (!d) return MPPI_ERR_INVALID;
+    if (mode != MPPI_LINK_POSITIONS_ZERO && mode != MPPI_LINK_POSITIONS_KINEMATIC)
+        return dfail(d, MPPI_ERR_INVALID, "link-position model must be MPPI_LINK_POSITIONS_ZERO or MPPI_LINK_POSITIONS_KINEMATIC");
+    d->link_positions = mode;
+    return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out)
+{
+    if (!d || !out) return MPPI_ERR_INVALID;
+    if (d->link_positions != MPPI_LINK_POSITIONS_KINEMATIC) {   // the stub: Vector3d::Zero()
+        for (int i = 0; i < 3 * MPPI_LINK_N; i++) out[i] = 0.0;
+        return MPPI_OK;
+    }
+    mppi_status st = obj_fetch(d);
+    if (st != MPPI_OK) return st;
+    static_assert(MPPI_LINK_N == FR_LINKS, "Link enum");
+    std::memcpy(out, d->h_obj->link, 3 * MPPI_LINK_N * sizeof(double));
+    return MPPI_OK;
+}
+
+const char *mppi_link_name(int link)
+{
+    static const char *const names[MPPI_LINK_N] = {"omni_base_root_link", "x_slider",    "y_slider",    "pivot",       "panda_link1",
+                                                   "panda_link2",         "panda_link3", "panda_link4", "panda_link5", "panda_link6",
+                                                   "panda_link7",         "panda_leftfinger", "panda_rightfinger"};
+    return (link >= 0 && link < MPPI_LINK_N) ? names[link] : nullptr;
 }
 
 }  // extern "C"
@@ -886,8 +945,11 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
         if (st != MPPI_OK) return fail(nullptr, st, why);
     }
 
+    int link_mode = 0;
+    if (!env_link_positions(link_mode, why)) return fail(nullptr, MPPI_ERR_INVALID, why);
     h = new mppi_handle();
     h->env = env;
+    if (dyn->kind == MPPI_DYNAMICS_FRANKARIDGEBACK) h->link_positions = link_mode;
     {
         const char *e = getenv("MPPI_HOST_TRACE");
         h->host_trace = e && e[0] == '1';
@@ -1490,6 +1552,9 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
     c.fsteps = a.fsteps;
     c.fcost = a.fcost;
     c.stats = cost_stats_used(h) ? h->d_cstats : nullptr;
+    c.link_positions = a.link_positions;
+    c.model = a.model;
+    c.dt = a.dt;
     return c;
 }
 
@@ -1522,6 +1587,7 @@ static mppi_status launch_filter_standalone(mppi_handle *h)
         a.cost_kind = h->cost_kind;
         a.energy = h->cost_kind == MPPI_COST_ASSISTED_MANIPULATION && h->am.enable_energy_limit;
         a.rec = h->d_rec_opt;
+        a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
         // the row's objective after its loop (fr_coop_kernel's one-wave path)
         a.costs_in_launch = fr_coop_costs_in_launch(h->env) ? 1 : 0;
         HIP_TRY(launch_fr_coop(a, h->stream_opt));
@@ -1665,6 +1731,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         a.rec = h->d_rec;
         a.rx = h->d_rx;
         a.rtoken = ++h->relay_token ? h->relay_token : ++h->relay_token;   // (never 0)
+        a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
         // sharded: this rank's wait timeouts into cost slot R, which the all-reduce carries to every rank
         a.wait_sum = h->comm ? h->d_costs_local + h->R : (sharded(h) ? h->d_costs + h->R : nullptr);
         if (h->debug_updates > 0) {   // mppi_debug_inject: this update's launch carries the fault
@@ -2210,6 +2277,28 @@ mppi_status mppi_debug_folded_cost(mppi_handle *h, double *cost)
     return MPPI_OK;
 }
 
+mppi_status mppi_set_link_positions(mppi_handle *h, int mode)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "link positions: FrankaRidgeback handles only");
+    if (mode != MPPI_LINK_POSITIONS_ZERO && mode != MPPI_LINK_POSITIONS_KINEMATIC)
+        return fail(h, MPPI_ERR_INVALID, "link-position model must be MPPI_LINK_POSITIONS_ZERO or MPPI_LINK_POSITIONS_KINEMATIC");
+    // the rollout launches' kernels are part of the launch plan and of a captured graph
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "the link-position model is set before the first update");
+    h->link_positions = mode;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_link_positions(mppi_handle *h, int *mode)
+{
+    if (!h || !mode) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "link positions: FrankaRidgeback handles only");
+    *mode = h->link_positions;
+    return MPPI_OK;
+}
+
 mppi_status mppi_set_graph(mppi_handle *h, int enable)
 {
     if (!h || enable < 0 || enable > 1) return MPPI_ERR_INVALID;
@@ -2481,7 +2570,8 @@ mppi_status mppi_optimal_terms(mppi_handle *h, double *terms7)
     }
     mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
     if (st != MPPI_OK) return st;
-    HIP_TRY(launch_fr_terms(h->d_cost, h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_terms, h->stream_opt));
+    HIP_TRY(launch_fr_terms(h->d_cost, h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_terms, h->stream_opt,
+                            h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? h->d_model : nullptr, h->dt));
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     std::memcpy(terms7, h->h_opt + 1, 7 * sizeof(double));

@@ -46,7 +46,8 @@ struct DevBarrier {
 
 // AssistedManipulation parameters in device form.  Per-step forecast-derived constants live in
 // StepConst; the self-collision term is a per-step constant for PinocchioDynamics (link
-// positions are the zero stub, pinocchio_dynamics.hpp:189-192) and is folded on the host.
+// positions are the zero stub, pinocchio_dynamics.hpp:189-192) and is folded on the host, unless
+// the handle runs the kinematic link-position model (sc_limit, sc_radii below).
 struct DevCost {
     int en_joint, en_self, en_work, en_energy, en_vel, en_traj, en_manip, pad0;
     DevBarrier lower[FR_NB], upper[FR_NB];
@@ -64,7 +65,17 @@ struct DevCost {
     DevBarrier tp_reach;                 // maximum_reach_limit (right)
     // energy_cost (assisted_manipulation.cpp:211-222): Left / Right barriers of the tank energy
     DevBarrier en_below, en_above;
+    // self_collision_cost on real link positions (the kinematic link-position model,
+    // mppi_set_link_positions): the active objective's self_collision_limit and the radii of the
+    // sphere links PIVOT, PANDA_LINK1..7 (radii[link - 3]).  Unread in the zero mode.
+    DevBarrier sc_limit;
+    double sc_radii[8];
 };
+
+// FrankaRidgeback::Link (frankaridgeback/dynamics.hpp:65-80): the universe, then bodies 0..11.  The
+// links self_collision_cost places a sphere on are SC_LINK0 .. SC_LINK0 + SC_LINKS - 1, bodies 2..9.
+constexpr int FR_LINKS = 13;
+constexpr int SC_LINK0 = 3, SC_LINKS = 8, SC_PAIRS = 20;
 
 // trajectory_cost() constants of step k (assisted_manipulation.cpp:237-290): everything that
 // depends only on the forecast wrench at t0 + k dt.

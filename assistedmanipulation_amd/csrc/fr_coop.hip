@@ -1200,6 +1200,7 @@ __device__ __forceinline__ double coop_solve(int j, const LaneConst &L, const Co
 // Jacobi rotations to its eigenvalues / vectors, l the least eigenvalue, a and b the other two
 // eigenvectors times sqrt(lambda - l) (inertias are positive semi-definite, so l >= 0 and the two
 // excesses are >= 0; rounding is clamped).
+#ifndef FR_COOP_LP_UNIT   // (the table kernel lives in the main unit alone)
 __device__ void inertia_rank2(const double *Ic, double *a, double *b, double *l)
 {
     double A[3][3] = {{Ic[0], Ic[1], Ic[3]}, {Ic[1], Ic[2], Ic[4]}, {Ic[3], Ic[4], Ic[5]}};
@@ -1293,6 +1294,7 @@ __global__ void fr_body_table_kernel(const DevModel *model, const DevCost *cost,
         table[t] = v;
     }
 }
+#endif   // FR_COOP_LP_UNIT
 
 // Stage the body table in LDS.
 __device__ __forceinline__ void stage_body_table(const FrRolloutArgs &a, double *Lmodel, int nt)
@@ -1646,15 +1648,22 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
 // parameters are the body table's T_LO .. T_VW fields (stride MB).
 
 // J of local rollout lr (or the folded filter() row) from its records, written out
-template <int CK, bool EN, bool KC>
+// (LP: the kinematic link-position model, fr_cost_terms.hpp record_self_collision)
+template <int CK, bool EN, bool KC, bool LP>
 __device__ __forceinline__ void launch_row_cost(const FrRolloutArgs &a, int64_t lr, int lane, const double *Lmodel)
 {
     const bool frow = a.fcost != nullptr && lr == a.count;
     if (!(lr < a.count || frow)) return;
     if (frow && (a.status->all_nan || a.status->sg_error)) return;   // no filter() when the update threw
-    const double J = mppi_cost::rollout_cost<CK, EN, MB, KC>(*a.cost, frow ? a.fsteps : a.steps,
-                                                              frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H,
-                                                              lane, Lmodel + T_LO);
+    double J;
+    if constexpr (LP)
+        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true>(*a.cost, frow ? a.fsteps : a.steps,
+                                                           frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H, lane,
+                                                           Lmodel + T_LO, mppi_cost::LinkModel{a.model, a.dt});
+    else
+        J = mppi_cost::rollout_cost<CK, EN, MB, KC>(*a.cost, frow ? a.fsteps : a.steps,
+                                                     frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H, lane,
+                                                     Lmodel + T_LO);
     if (lane == 0) {
         if (frow) *a.fcost = J;
         else {
@@ -1832,7 +1841,7 @@ __device__ __forceinline__ bool chunk_ready(const FrRolloutArgs &a, int g, int c
 }
 
 // The step costs of chunk c of group g into Lcs; the pass that completes the group sums its rows
-template <int CK, bool EN>
+template <int CK, bool EN, bool LP>
 __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c, int lane, const double *Lmodel, double *Lcs,
                                           int *Lq)
 {
@@ -1848,7 +1857,12 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
     const StepConst *stp = frow ? a.fsteps : a.steps;
     const int kk = live ? k : 0;
     PMARK(8);
-    double cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO);
+    double cs;
+    if constexpr (LP)
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO,
+                                                                     mppi_cost::LinkModel{a.model, a.dt}, kk == 0);
+    else
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO);
     PMARK_D(9, cs);
     if (live) Lcs[(g * ROWS_PER_WAVE + i) * HC_MAX + k] = cs;
     // the stores before the count: the wave that completes the group reads every chunk's costs
@@ -1908,7 +1922,7 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
 // A wave's objective work: chunks of any group, its own group (first) first, each taken from the
 // group's counter when it is ready (a chunk taken just as another wave took the one before it
 // waits for its records); returns once every chunk is taken.  Bounded.
-template <int CK, bool EN>
+template <int CK, bool EN, bool LP>
 __device__ __forceinline__ void cost_work(const FrRolloutArgs &a, int first, int ng, int lane, const double *Lmodel,
                                          double *Lcs, int *Lflag, int *Lq)
 {
@@ -1937,7 +1951,7 @@ __device__ __forceinline__ void cost_work(const FrRolloutArgs &a, int first, int
 #ifdef COST_TRACE   // block 0's chunks: start, end, wave (slots past the relay's)
             const uint32_t tc0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
-            cost_chunk<CK, EN>(a, g, c, lane, Lmodel, Lcs, Lq);
+            cost_chunk<CK, EN, LP>(a, g, c, lane, Lmodel, Lcs, Lq);
 #ifdef COST_TRACE
             if (a.trace && blockIdx.x == 0 && lane == 0 && c < 4) {
                 uint32_t *tr = a.trace + 4 * (gridDim.x * 4 + 16 + 4 * g + c);
@@ -1963,14 +1977,14 @@ __device__ __forceinline__ void group_draws(const FrRolloutArgs &a, int g, int l
 
 // fr_coop_kernel's four-wave launch (no rows left over): each main wave evaluates its own rows'
 // objective after its loop (rollout_cost, a pass per row, lane = step) and makes their next draws
-template <int CK, bool EN, bool KC>
+template <int CK, bool EN, bool KC, bool LP>
 __device__ __forceinline__ void launch_costs(const FrRolloutArgs &a, int wv, int lane, const double *Lmodel)
 {
     const int64_t w0 = (int64_t)blockIdx.x * 4;
     __builtin_amdgcn_s_waitcnt(0);   // the wave's own record stores, read back by other lanes
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 #pragma unroll 1
-    for (int i = 0; i < ROWS_PER_WAVE; i++) launch_row_cost<CK, EN, KC>(a, (w0 + wv) * ROWS_PER_WAVE + i, lane, Lmodel);
+    for (int i = 0; i < ROWS_PER_WAVE; i++) launch_row_cost<CK, EN, KC, LP>(a, (w0 + wv) * ROWS_PER_WAVE + i, lane, Lmodel);
     if (a.ahead_noise) tail_draws(a, (w0 + wv) * ROWS_PER_WAVE, lane);
 }
 
@@ -2136,47 +2150,27 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // on the free CU (per-block traces, tools/wave_trace.py).
 // KC: compact records with the kinematic sums on the rows' chains (the update's launches, throughput-
 // bound); the standalone filter() row (one latency-bound row) keeps the 768-B record and a shorter step.
+// LP: the objective of the kinematic link-position model (FrRolloutArgs::link_positions).  The
+// kernels' body is shared text (fr_coop_kernel_body.inc, fr_coop_x_kernel_body.inc); the LP = true
+// versions are kernels of their own (fr_coop_lp_kernel, fr_coop_x_lp_kernel) in a translation unit
+// of their own (fr_coop_lp.hip, which includes this file with FR_COOP_LP_UNIT): in one unit with the
+// default mode's kernels they changed fr_coop_x_kernel's scalar code, and apart the default mode's
+// are the same functions, by name and by instruction.
+#ifndef FR_COOP_LP_UNIT
 template <int CK, bool EN, int WPB, bool KC>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_kernel(FrRolloutArgs a)
 {
-    constexpr int KS = EN ? LDS_KIN_EN : LDS_KIN;
-    __shared__ __attribute__((aligned(16))) double lds_kin[WPB * ROWS_PER_WAVE * KS];
-    __shared__ __attribute__((aligned(16))) double lds_scr[WPB * ROWS_PER_WAVE * LDS_SCR];
-    __shared__ double Lmodel[LDS_MODEL];
-    __shared__ double Lx0[MAX_X];
-    if (a.optimal && (a.status->all_nan || a.status->sg_error)) return;   // no filter() (mppi.cpp:170-176)
-    const int wv = (WPB == 1) ? 0 : (int)(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int rowi = lane >> 4;
-    const int wrow = wv * ROWS_PER_WAVE + rowi;   // row within the workgroup
-    const int wblk = blockIdx.x * WPB + wv;        // wave index in the launch
-    int rk = 0x7FFFFFFF;
-    if constexpr (WPB == 4) rk = kept_rank(a, (int64_t)wblk * ROWS_PER_WAVE + rowi);
-    stage_body_table(a, Lmodel, 64 * WPB);
-    stage_x0(a, Lx0);
-    __syncthreads();
-    if constexpr (WPB == 4) {
-        if (a.drawn_ahead) {
-            if (blockIdx.x == 0 && wv == 1) block0_sample_writes<64>(a, lane);
-            kept_rows_wave(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, rk);
-        }
-    }
-    coop_rows<CK, EN, false, 0, false, KC>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, lds_kin + wrow * KS,
-                                           lds_scr + wrow * LDS_SCR, Lmodel, Lx0);
-    if constexpr (WPB == 4) {
-        if (a.costs_in_launch) launch_costs<CK, EN, KC>(a, wv, lane, Lmodel);
-    } else if constexpr (WPB == 1) {
-        // past one round (two waves per SIMD, several rounds): the wave's own rows' objective after
-        // its loop, while the launch's other waves still run, instead of fr_step_cost_kernel after it
-        if (a.costs_in_launch) {
-            __builtin_amdgcn_s_waitcnt(0);   // the wave's own record stores, read back by other lanes
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#pragma unroll 1
-            for (int i = 0; i < ROWS_PER_WAVE; i++)
-                launch_row_cost<CK, EN, KC>(a, (int64_t)blockIdx.x * ROWS_PER_WAVE + i, lane, Lmodel);
-        }
-    }
+    constexpr bool LP = false;
+#include "fr_coop_kernel_body.inc"
 }
+#else
+template <int CK, bool EN, int WPB, bool KC>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_lp_kernel(FrRolloutArgs a)
+{
+    constexpr bool LP = true;
+#include "fr_coop_kernel_body.inc"
+}
+#endif
 
 
 // The update's launch: four waves of main rows per workgroup (rollouts [0, xbase)) and four more
@@ -2185,78 +2179,21 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
 // extra rows [xbase, count) plus the folded filter() row, xrows of them, four per workgroup) those
 // four waves first carry the rows left over through the horizon, a quarter each (relay_stage).
 constexpr int XW = 8;
+#ifndef FR_COOP_LP_UNIT
 template <int CK, bool EN>
 __global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_x_kernel(FrRolloutArgs a)
 {
-    constexpr int KS = EN ? LDS_KIN_EN : LDS_KIN;
-    __shared__ __attribute__((aligned(16))) double lds_kin[5 * ROWS_PER_WAVE * KS];
-    __shared__ __attribute__((aligned(16))) double lds_scr[5 * ROWS_PER_WAVE * LDS_SCR];
-    __shared__ double Lmodel[LDS_MODEL];
-    __shared__ double Lx0[MAX_X];
-    __shared__ int Lflag[LF_N];      // records stored (main waves, relay), kept columns copied
-    __shared__ int Lq[Q_N];          // the main waves' steps, chunk counters, the relay's stage
-    __shared__ double Lst[64 * 3];   // the relay's (q, qd, E) per lane between stages
-    __shared__ __attribute__((aligned(16))) double Lcs[5 * ROWS_PER_WAVE * HC_MAX];   // step costs of the groups' rows
-    const int wv = (int)(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int rowi = lane >> 4;
-    const int member = relay_member(a);   // of the relay rows this workgroup carries (-1: none)
-    const bool xr = member >= 0;
-    const int64_t lr = wv < 4 ? (int64_t)(blockIdx.x * 4 + wv) * ROWS_PER_WAVE + rowi
-                              : a.xbase + (int64_t)((int)blockIdx.x % RELAY_STRIDE) * ROWS_PER_WAVE + rowi;   // (waves < 5)
-    const int rk = (wv < 4 || (wv == 4 && xr)) ? kept_rank(a, lr) : 0x7FFFFFFF;
-    stage_body_table(a, Lmodel, 64 * XW);
-    stage_x0(a, Lx0);
-    if (threadIdx.x < LF_N) Lflag[threadIdx.x] = 0;
-    if (threadIdx.x < Q_N) Lq[threadIdx.x] = threadIdx.x < Q_NEXT ? -1 : 0;
-    const int ng = xr ? 5 : 4;   // row groups of the objective
-    if (threadIdx.x == Q_NEXT + 4) {   // the relay group's first chunk here (none: past every chunk)
-        int cb, ce;
-        group_chunks(a, 4, cb, ce);
-        Lq[Q_NEXT + 4] = xr ? cb : 0x7FFF;
-    }
-    __syncthreads();
-    // main wave w's rows use slots 4 w + i, the relay's rows (whichever wave runs them) 16 + i
-    const int slot = wv < 4 ? wv * ROWS_PER_WAVE + rowi : 4 * ROWS_PER_WAVE + rowi;
-    double *Lk = lds_kin + slot * KS, *Lw = lds_scr + slot * LDS_SCR;
-    if (a.drawn_ahead) {
-        if (blockIdx.x == 0 && wv == 1) block0_sample_writes<64>(a, lane);   // off the SIMD of the relay's first stage
-        if (wv < 4) kept_rows_wave(a, lr, lane, rk);
-        else if (wv == 4 && xr) {   // the relay rows' columns of the steps this member runs
-            kept_rows_wave(a, lr, lane, rk, relay_member_step(a, member, a.H),
-                           member + 1 < a.relay_k ? relay_member_step(a, member + 1, a.H) : 0x7FFFFFFF);
-            __hip_atomic_store(Lflag + LF_KEPT_X, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-    const bool cil = a.costs_in_launch != 0;
-    if (wv < 4) {
-        if (cil) {   // the next draws for this wave's rows may now overwrite their previous eps
-            __builtin_amdgcn_s_waitcnt(0);
-            __hip_atomic_store(Lflag + LF_KEPT + wv, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_s_setprio(1);   // above the objective's waves, below the relay
-        }
-        const int wblk = blockIdx.x * 4 + wv;
-        coop_rows<CK, EN, false, 0, true>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, Lk, Lw, Lmodel, Lx0,
-                                          nullptr, 0, 0x7FFFFFFF, Lq + Q_PROG + wv);
-        __builtin_amdgcn_s_setprio(0);
-        if (cil) {
-            signal_records(Lflag + wv);
-            cost_work<CK, EN>(a, wv, ng, lane, Lmodel, Lcs, Lflag, Lq);
-        }
-#ifdef COST_TRACE   // COOP_TRACE builds: slot 3 = the wave's end (after its objective work)
-        if (a.trace && lane == 0) a.trace[4 * wblk + 3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#endif
-    } else {
-        const int s = wv - 4;   // this wave's SIMD
-        const bool relay = xr && (s == 0 || a.handover);
-        if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst);
-        if (!cil) return;
-        // the draws for main wave s's rows (relay stages made theirs before their stage; wave 0's
-        // rows of a workgroup with rows left over are left to rank_draw_kernel)
-        if (a.ahead_noise && !relay && !(member == 0 && s == 0)) group_draws(a, s, lane, Lflag);
-        cost_work<CK, EN>(a, s, ng, lane, Lmodel, Lcs, Lflag, Lq);
-    }
+    constexpr bool LP = false;
+#include "fr_coop_x_kernel_body.inc"
 }
+#else
+template <int CK, bool EN>
+__global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_x_lp_kernel(FrRolloutArgs a)
+{
+    constexpr bool LP = true;
+#include "fr_coop_x_kernel_body.inc"
+}
+#endif
 
 namespace mppi_eng {
 
@@ -2273,27 +2210,72 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
     return at.sharedSizeBytes >= want ? 0u : (unsigned)(want - at.sharedSizeBytes);
 }
 
+// The kinematic link-position model's launches (fr_coop_lp.hip): the x kernel, and fr_coop_lp_kernel
+// with wpb waves per workgroup and compact or 768-B records
+void launch_fr_coop_lp_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);
+void launch_fr_coop_lp_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact);
+bool fr_coop_lp_is_update_kernel(const void *func);   // an fr_coop_x_lp_kernel instantiation
+
+#ifdef FR_COOP_LP_UNIT
+#define FR_COOP_K fr_coop_lp_kernel
+#define FR_COOP_XK fr_coop_x_lp_kernel
+#else
+#define FR_COOP_K fr_coop_kernel
+#define FR_COOP_XK fr_coop_x_kernel
+#endif
+
 template <int CK, bool EN, int WPB, bool KC>
 static void launch_k(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-    static const unsigned pad = one_per_cu_pad(fr_coop_kernel<CK, EN, WPB, KC>, WPB);
-    hipLaunchKernelGGL((fr_coop_kernel<CK, EN, WPB, KC>), dim3(nb), dim3(64 * WPB), pad, s, a);
+    static const unsigned pad = one_per_cu_pad(FR_COOP_K<CK, EN, WPB, KC>, WPB);
+    hipLaunchKernelGGL((FR_COOP_K<CK, EN, WPB, KC>), dim3(nb), dim3(64 * WPB), pad, s, a);
 }
 
 template <int CK, bool EN>
 static void launch_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-    static const unsigned pad = one_per_cu_pad(fr_coop_x_kernel<CK, EN>, XW);
-    hipLaunchKernelGGL((fr_coop_x_kernel<CK, EN>), dim3(nb), dim3(64 * XW), pad, s, a);
+    static const unsigned pad = one_per_cu_pad(FR_COOP_XK<CK, EN>, XW);
+    hipLaunchKernelGGL((FR_COOP_XK<CK, EN>), dim3(nb), dim3(64 * XW), pad, s, a);
 }
 
 template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
+#ifndef FR_COOP_LP_UNIT
+    if (a.link_positions) return launch_fr_coop_lp_one(a, nb, s, WPB, KC);
+#endif
     if (a.cost_kind == CK_TRACK_POINT) launch_k<CK_TRACK_POINT, false, WPB, KC>(a, nb, s);
     else if (a.energy) launch_k<CK_ASSISTED_MANIPULATION, true, WPB, KC>(a, nb, s);
     else launch_k<CK_ASSISTED_MANIPULATION, false, WPB, KC>(a, nb, s);
 }
+
+static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
+{
+#ifndef FR_COOP_LP_UNIT
+    if (a.link_positions) return launch_fr_coop_lp_x(a, nb, s);
+#endif
+    if (a.cost_kind == CK_TRACK_POINT) launch_x<CK_TRACK_POINT, false>(a, nb, s);
+    else if (a.energy) launch_x<CK_ASSISTED_MANIPULATION, true>(a, nb, s);
+    else launch_x<CK_ASSISTED_MANIPULATION, false>(a, nb, s);
+}
+
+#ifdef FR_COOP_LP_UNIT
+void launch_fr_coop_lp_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s) { launch_x_any(a, nb, s); }
+
+void launch_fr_coop_lp_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact)
+{
+    if (wpb == 4) launch_one<4, true>(a, nb, s);   // (the four-wave launch writes compact records only)
+    else if (compact) launch_one<1, true>(a, nb, s);
+    else launch_one<1, false>(a, nb, s);
+}
+
+bool fr_coop_lp_is_update_kernel(const void *f)
+{
+    return f == (const void *)&fr_coop_x_lp_kernel<CK_ASSISTED_MANIPULATION, false> ||
+           f == (const void *)&fr_coop_x_lp_kernel<CK_ASSISTED_MANIPULATION, true> ||
+           f == (const void *)&fr_coop_x_lp_kernel<CK_TRACK_POINT, false>;
+}
+#else
 
 bool fr_coop_compact(const FrRolloutArgs &a) { return !a.optimal; }
 
@@ -2322,14 +2304,7 @@ bool fr_coop_is_update_kernel(const void *f)
 {
     return f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, false> ||
            f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
-           f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false>;
-}
-
-static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
-{
-    if (a.cost_kind == CK_TRACK_POINT) launch_x<CK_TRACK_POINT, false>(a, nb, s);
-    else if (a.energy) launch_x<CK_ASSISTED_MANIPULATION, true>(a, nb, s);
-    else launch_x<CK_ASSISTED_MANIPULATION, false>(a, nb, s);
+           f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f);
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at
@@ -2382,5 +2357,7 @@ hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const CoopPlan &p, hipS
     if (e1) (void)hipEventRecord(e1, s);
     return hipGetLastError();
 }
+
+#endif   // FR_COOP_LP_UNIT
 
 }  // namespace mppi_eng

@@ -35,41 +35,32 @@ using namespace mppi_cost;
 // lanes: every byte of the rollout's records is used once, through L2).  Staging through LDS took
 // 21.5 KB per wave and held a CU to seven waves, too few to hide the loads; without it the kernel
 // is bounded by registers (four waves per SIMD).
+// LP: the kinematic link-position model (FrCostArgs::link_positions): the self-collision term from
+// each record's link positions (fr_cost_terms.hpp record_self_collision)
+// (a kernel of its own, fr_step_cost_lp_kernel, from the same text: the default mode's keep their names and instructions)
 template <int CK, bool EN, bool KC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void fr_step_cost_kernel(FrCostArgs a)
 {
-    __shared__ double Lj[FR_NB * JT_STRIDE];
-    const int lane = threadIdx.x;
-    const int64_t row = blockIdx.x;
-    const bool frow = a.fcost != nullptr && row == a.count;
-    // no filter() when the update threw (mppi.cpp:170-176)
-    if ((frow || a.optimal) && (a.status->all_nan || a.status->sg_error)) return;
-    const int H = a.H;
-    const StepConst *stp = frow ? a.fsteps : a.steps;
-    const DevCost &Cs = *a.cost;
-    if (CK != CK_TRACK_POINT)   // per-joint parameters (84 of them for 64 lanes)
-        for (int i = lane; i < FR_NB * JT_STRIDE; i += 64) {
-            const int j = i / JT_STRIDE, f = i - j * JT_STRIDE;
-            const double *src = f < 3 ? &Cs.lower[j].bound + f : (f < 6 ? &Cs.upper[j].bound + (f - 3) : &Cs.vel_q[j]);
-            Lj[i] = *src;
-        }
-    __syncthreads();
-    const double J = rollout_cost<CK, EN, JT_STRIDE, KC>(Cs, stp, frow ? a.frec : a.rec + row * H * (KC ? FR_REC_C : FR_REC), H,
-                                                         lane, Lj);
-    if (lane != 0) return;
-    if (frow) *a.fcost = J;
-    else if (a.optimal) *a.cost_out = J;
-    else {
-        a.cost_out[a.begin + row] = J;
-        fold_cost_stats(a.stats, J, row);   // exact min / max / count, any order
-    }
+    constexpr bool LP = false;
+#include "fr_step_cost_kernel_body.inc"
+}
+// Two waves per SIMD here: the link positions and the pose are live beside the barrier chains, and
+// at four waves (128 VGPRs) this kernel spilled 84-164 of them; 0.223 against 0.300 ms/update at
+// 4096 x 64 with MPPI_COSTS_IN_LAUNCH=0 (profiles/link_positions/bench_costkernel_*).
+template <int CK, bool EN, bool KC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_lp_kernel(FrCostArgs a)
+{
+    constexpr bool LP = true;
+#include "fr_step_cost_kernel_body.inc"
 }
 
 // The optimal rollout's per-term totals (AssistedManipulation's accumulators after filter(),
 // mppi.cpp:450-479 with thread 0's cost, reset at its start): one wave over the filter() row's
 // records, lane = step, each term summed over the steps in step order (m_*_cost += per step).
+// model != null: the kinematic link-position model, the self-collision total from the records' link
+// positions.
 __global__ __launch_bounds__(64) void fr_terms_kernel(const DevCost *cost, const StepConst *steps, const double *rec, int H,
-                                                      int compact, double *out7)
+                                                      int compact, double *out7, const DevModel *model, double dt)
 {
     const int lane = threadIdx.x;
     double tot[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -78,7 +69,14 @@ __global__ __launch_bounds__(64) void fr_terms_kernel(const DevCost *cost, const
         const int k = base + (lane < n ? lane : 0);
         double t[7], r[FR_NREC];
         derive_record(rec + (int64_t)k * (compact ? FR_REC_C : FR_REC), r, compact != 0);
-        assisted_manipulation_terms(*cost, steps[k], r, r[REC_QQD + 4], t);
+        if (model) {
+            double qj[10], lp[SC_LINKS][3];
+            for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
+            link_fk(*model, qj, lp);
+            assisted_manipulation_terms(*cost, steps[k], r, r[REC_QQD + 4], t, lp);
+        } else {
+            assisted_manipulation_terms(*cost, steps[k], r, r[REC_QQD + 4], t);
+        }
 #pragma unroll
         for (int m = 0; m < 7; m++)
             for (int i = 0; i < n; i++) tot[m] += readlane_f64(t[m], i);
@@ -96,9 +94,9 @@ __global__ __launch_bounds__(64) void fr_terms_kernel(const DevCost *cost, const
 namespace mppi_eng {
 
 hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const double *rec, int H, bool compact, double *out7,
-                           hipStream_t s)
+                           hipStream_t s, const DevModel *link_model, double dt)
 {
-    hipLaunchKernelGGL(fr_terms_kernel, dim3(1), dim3(64), 0, s, cost, steps, rec, H, compact ? 1 : 0, out7);
+    hipLaunchKernelGGL(fr_terms_kernel, dim3(1), dim3(64), 0, s, cost, steps, rec, H, compact ? 1 : 0, out7, link_model, dt);
     return hipGetLastError();
 }
 
@@ -108,7 +106,18 @@ hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s)
     if (rows == 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(64);
     // the records' layout is the launch's that wrote them (FrCostArgs::compact)
-    if (a.compact) {
+    if (a.link_positions) {
+        if (!a.model) return hipErrorInvalidValue;
+        if (a.compact) {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
+        } else {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
+        }
+    } else if (a.compact) {
         if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
         else if (a.energy) hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);

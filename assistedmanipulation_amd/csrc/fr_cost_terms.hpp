@@ -51,6 +51,110 @@ __device__ __forceinline__ double left_barrier(double bound, double scale, doubl
 __device__ __forceinline__ double right_barrier(const DevBarrier &b, double v) { return right_barrier(b.bound, b.scale, b.max, v); }
 __device__ __forceinline__ double left_barrier(const DevBarrier &b, double v) { return left_barrier(b.bound, b.scale, b.max, v); }
 
+// ---- the kinematic link-position model (mppi_set_link_positions) -------------------------------
+// get_link_position(L) = the world translation of body L - 1 at the last calculate().  A step
+// record holds x_k and the kinematics of the calculate() before it, which ran at q_{k-1} (at q_0
+// for record 0: set_state's).  The rollout's Euler step is q_k = q_{k-1} + qd_k dt for every joint
+// (the base's too: its qd is overwritten before the step), so the record itself gives that
+// configuration back, q_{k-1} = q_k - qd_k dt to one rounding of q: no record is widened and no
+// lane reads the previous step's record (which another workgroup may have written, the relay).
+// first: record 0.
+__device__ __forceinline__ double lagged_q(double q, double qd, double dt, bool first)
+{
+    return first ? q : __builtin_fma(-qd, dt, q);
+}
+
+// World translations of bodies 2..9 (the sphere links PIVOT, PANDA_LINK1..7) at joint positions
+// qj[0..9]: fk_bodies' chain (fr_object.hip), pose_i = pose_parent o placement_i o joint_i, term for
+// term, with the rollout kernel's fsincos.  Bodies 0..9 are one chain (FR_PARENT[i] = i - 1).
+__device__ __forceinline__ void link_fk(const DevModel &M, const double *qj, double (*lp)[3])
+{
+    const SinCosK K = sincos_constants();
+    double R[9], p[3];
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+        const DevBody &b = M.b[i];
+        double Rl[9], pl[3];
+        if (FR_KIND[i] == KIND_RZ) {
+            double s, c;
+            fsincos(qj[i], &s, &c, K);
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                Rl[3 * r + 0] = b.R[3 * r + 0] * c + b.R[3 * r + 1] * s;
+                Rl[3 * r + 1] = b.R[3 * r + 0] * (-s) + b.R[3 * r + 1] * c;
+                Rl[3 * r + 2] = b.R[3 * r + 2];
+                pl[r] = b.p[r];
+            }
+        } else {
+            const int col = FR_KIND[i] == KIND_PX ? 0 : 1;
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) Rl[3 * r + k] = b.R[3 * r + k];
+                pl[r] = b.p[r] + b.R[3 * r + col] * qj[i];
+            }
+        }
+        if (i == 0) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) R[k] = Rl[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) p[k] = pl[k];
+        } else {
+            double Rn[9], pn[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+#pragma unroll
+                for (int cc = 0; cc < 3; cc++) Rn[3 * r + cc] = (R[3 * r] * Rl[cc] + R[3 * r + 1] * Rl[3 + cc]) + R[3 * r + 2] * Rl[6 + cc];
+                pn[r] = p[r] + ((R[3 * r] * pl[0] + R[3 * r + 1] * pl[1]) + R[3 * r + 2] * pl[2]);
+            }
+#pragma unroll
+            for (int k = 0; k < 9; k++) R[k] = Rn[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) p[k] = pn[k];
+        }
+        if (i >= SC_LINK0 - 1) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) lp[i - (SC_LINK0 - 1)][k] = p[k];
+        }
+    }
+}
+
+// self_collision_cost over the 20 sphere pairs, in the reference's pair order, on the sphere links'
+// positions lp[link - 3]: AssistedManipulation passes distance - radii through the left barrier
+// (assisted_manipulation.cpp:127-153), TrackPoint radii - distance (track_point.cpp:118-144).
+template <bool TP>
+__device__ __forceinline__ double self_collision_term(const DevCost &Cs, const double (*lp)[3])
+{
+    constexpr int A[SC_PAIRS] = {0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5};
+    constexpr int B[SC_PAIRS] = {3, 4, 5, 6, 7, 3, 4, 5, 6, 7, 4, 5, 6, 7, 5, 6, 7, 6, 7, 7};
+    double cost = 0.0;
+#pragma unroll
+    for (int n = 0; n < SC_PAIRS; n++) {
+        const double d0 = lp[A[n]][0] - lp[B[n]][0], d1 = lp[A[n]][1] - lp[B[n]][1], d2 = lp[A[n]][2] - lp[B[n]][2];
+        const double distance = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        const double radii = Cs.sc_radii[A[n]] + Cs.sc_radii[B[n]];
+        cost += left_barrier(Cs.sc_limit, TP ? radii - distance : distance - radii);
+    }
+    return cost;
+}
+
+// The term of one step record from its own (q, qd) pairs at pq[2j], pq[2j + 1]
+template <bool TP>
+__device__ __forceinline__ double record_self_collision(const DevCost &Cs, const DevModel &M, const double *pq, double dt, bool first)
+{
+    double qj[10], lp[SC_LINKS][3];
+#pragma unroll
+    for (int j = 0; j < 10; j++) qj[j] = lagged_q(pq[2 * j], pq[2 * j + 1], dt, first);
+    link_fk(M, qj, lp);
+    return self_collision_term<TP>(Cs, lp);
+}
+
+// What the kinematic mode's objective needs beside the record: the model and the rollout's time step
+struct LinkModel {
+    const DevModel *model;
+    double dt;
+};
+
 // Per-joint parameters of the objective in LDS, joint j at Lj[j JS ..]: lower barrier (bound,
 // scale, max), upper barrier, velocity weight - uniform loads next to their use instead of 84
 // scalar registers the compiler loaded up front and spilled.  fr_cost.hip stages them with stride
@@ -131,9 +235,12 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 
 // AssistedManipulation::get_cost at the record's state with its kinematics (KC: a compact record,
 // J v and J_a J_a^T stored; else the 768-B record, whose motion subspaces they are formed from)
-template <bool EN, int JS, bool KC = false, int JG = 1>
+// LP: the kinematic link-position model - the self-collision term from the record's link positions
+// (lm, first: record_self_collision) instead of the zero stub's constant
+template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
-                                                             const double *Lj, const double2 *src)
+                                                             const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
+                                                             bool first = false)
 {
     double j0 = 0.0, j1 = 0.0, v0 = 0.0, v1 = 0.0;
     int off = 0;
@@ -218,7 +325,13 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
     }
     double cost = 0.0;
     cost += Cs.en_joint ? joint : 0.0;
-    cost += Cs.en_self ? Cs.self_collision : 0.0;
+    if constexpr (LP) {   // the (q, qd) pairs again, from the stored record (r holds its tail by now)
+        double sct = 0.0;
+        if (Cs.en_self) sct = record_self_collision<false>(Cs, *lm.model, reinterpret_cast<const double *>(tp), lm.dt, first);
+        cost += sct;
+    } else {
+        cost += Cs.en_self ? Cs.self_collision : 0.0;
+    }
     cost += Cs.en_work ? wc : 0.0;
     if constexpr (EN) {   // energy_cost (:211-222)
         const double E = r[REC_E];
@@ -238,8 +351,9 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
 // rollout's totals only (mppi_optimal_terms) and the standalone get_cost, so off the rollout
 // kernels' path.  yaw: dynamics->get_state()[2] (workspace_cost, :160-168; in a rollout the
 // record's q_2).
+// lp: the sphere links' positions (kinematic link-position model), or null: the zero stub's constant.
 __device__ __forceinline__ void assisted_manipulation_terms(const DevCost &Cs, const StepConst &sc, const double *r, double yaw,
-                                                            double *t)
+                                                            double *t, const double (*lp)[3] = nullptr)
 {
     double j0 = 0.0, j1 = 0.0, v0 = 0.0, v1 = 0.0;
     for (int j = 0; j < FR_NB; j++) {
@@ -274,7 +388,7 @@ __device__ __forceinline__ void assisted_manipulation_terms(const DevCost &Cs, c
     }
     const double E = r[REC_E];
     t[0] = Cs.en_joint ? j0 + j1 : 0.0;
-    t[1] = Cs.en_self ? Cs.self_collision : 0.0;
+    t[1] = Cs.en_self ? (lp ? self_collision_term<false>(Cs, lp) : Cs.self_collision) : 0.0;
     t[2] = Cs.en_work ? wc : 0.0;
     t[3] = Cs.en_energy ? left_barrier(Cs.en_below, E) + right_barrier(Cs.en_above, E) : 0.0;
     t[4] = Cs.en_vel ? v0 + v1 : 0.0;
@@ -285,7 +399,10 @@ __device__ __forceinline__ void assisted_manipulation_terms(const DevCost &Cs, c
 // TrackPoint::get_cost: the joint terms sum joints 0..9 in order; reach_cost's robot point is the
 // arm mount + R_z(yaw) (0.3, 0, 0.15) (track_point.cpp:162-186), yaw = dynamics->get_state()[2]
 // (in a rollout the record's own q_2)
-__device__ __forceinline__ double track_point_cost(const DevCost &Cs, const double *r, double yaw)
+// LP: the self-collision term on the sphere links' positions lp (kinematic link-position model),
+// else the zero stub's constant
+template <bool LP = false>
+__device__ __forceinline__ double track_point_cost(const DevCost &Cs, const double *r, double yaw, const double (*lp)[3] = nullptr)
 {
     const double *ee = r + REC_EE, *am = r + REC_AM;
     const double d0 = ee[0] - Cs.tp_point[0], d1 = ee[1] - Cs.tp_point[1], d2 = ee[2] - Cs.tp_point[2];
@@ -308,7 +425,13 @@ __device__ __forceinline__ double track_point_cost(const DevCost &Cs, const doub
     const double t0 = ee[0] - (am[0] + off0), t1 = ee[1] - (am[1] + off1), t2 = ee[2] - (am[2] + off2);
     const double reach = right_barrier(Cs.tp_reach, sqrt((t0 * t0 + t1 * t1) + t2 * t2));
     cost += Cs.tp_en_joint ? joint : 0.0;
-    cost += Cs.tp_en_self ? Cs.tp_self : 0.0;
+    if constexpr (LP) {
+        double sct = 0.0;
+        if (Cs.tp_en_self) sct = self_collision_term<true>(Cs, lp);
+        cost += sct;
+    } else {
+        cost += Cs.tp_en_self ? Cs.tp_self : 0.0;
+    }
     cost += Cs.tp_en_reach ? reach : 0.0;
     return cost;
 }
@@ -322,18 +445,34 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
 
 // gamma_k times the objective at step record r (AssistedManipulation: r holds the record's (q, qd)
 // pairs, the rest is read from the stored record src; TrackPoint: r holds the record up to REC_VL)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false>
 __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &sc, const double *r, const double *Lj,
-                                           const double2 *src)
+                                           const double2 *src, LinkModel lm = LinkModel{}, bool first = false)
 {
-    if constexpr (CK == CK_TRACK_POINT) return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4]);
-    else return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG>(Cs, sc, r, Lj, src);
+    if constexpr (CK == CK_TRACK_POINT) {
+        if constexpr (LP) {
+            double lp[SC_LINKS][3];
+            if (Cs.tp_en_self) {
+                double qj[10];
+#pragma unroll
+                for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], lm.dt, first);
+                link_fk(*lm.model, qj, lp);
+            }
+            return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
+        } else {
+            return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4]);
+        }
+    } else {
+        if constexpr (LP) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
+        else return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG>(Cs, sc, r, Lj, src);
+    }
 }
 
 // gamma_k times the objective at the stored step record rk (FR_REC doubles, or FR_REC_C with KC;
 // 16-byte aligned)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1>
-__device__ __forceinline__ double record_step_cost(const DevCost &Cs, const StepConst &sc, const double *rk, const double *Lj)
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false>
+__device__ __forceinline__ double record_step_cost(const DevCost &Cs, const StepConst &sc, const double *rk, const double *Lj,
+                                                  LinkModel lm = LinkModel{}, bool first = false)
 {
     double r[FR_NREC];
     const double2 *src = reinterpret_cast<const double2 *>(rk);
@@ -344,7 +483,8 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
         r[2 * i] = v.x;
         r[2 * i + 1] = v.y;
     }
-    return step_cost<CK, EN, JS, KC, JG>(Cs, sc, r, Lj, src);
+    if constexpr (LP) return step_cost<CK, EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
+    else return step_cost<CK, EN, JS, KC, JG>(Cs, sc, r, Lj, src);
 }
 
 // J of one rollout from its H stored step records (rollout-major, FR_REC doubles each, FR_REC_C with
@@ -352,16 +492,18 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
 // lane k evaluates step k (64 steps a pass) and the wave sums the step costs in step order, as the
 // reference accumulates J += cost (mppi.cpp:322-337); a NaN step makes the sum NaN (the reference's
 // early stop), canonicalised to the quiet NaN it stores.  The same value on every lane.
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, bool LP = false>
 __device__ __forceinline__ double rollout_cost(const DevCost &Cs, const StepConst *stp, const double *rec, int H, int lane,
-                                               const double *Lj)
+                                               const double *Lj, LinkModel lm = LinkModel{})
 {
     constexpr int RS = KC ? FR_REC_C : FR_REC;
     double J = 0.0;
     for (int base = 0; base < H; base += 64) {
         const int n = (H - base < 64) ? H - base : 64;
         const int k = base + (lane < n ? lane : 0);
-        const double c = record_step_cost<CK, EN, JS, KC>(Cs, stp[k], rec + (int64_t)k * RS, Lj);
+        double c;
+        if constexpr (LP) c = record_step_cost<CK, EN, JS, KC, 1, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0);
+        else c = record_step_cost<CK, EN, JS, KC>(Cs, stp[k], rec + (int64_t)k * RS, Lj);
         // J += c_i in step order; the lane reads eight at a time, ahead of their adds
         int i = 0;
         for (; i + 8 <= n; i += 8) {

@@ -310,6 +310,11 @@ __device__ void calculate(const DevModel &M, DevPinocchio &P)
     J[2 * FR_NB] = 0.0; J[2 * FR_NB + 1] = 0.0; J[2 * FR_NB + 2] = 1.0;
     const double *R2 = B.R[FR_AM_PARENT], *p2 = B.p[FR_AM_PARENT];
     for (int r = 0; r < 3; r++) P.am[r] = p2[r] + ((R2[3 * r] * M.am_p[0] + R2[3 * r + 1] * M.am_p[1]) + R2[3 * r + 2] * M.am_p[2]);
+    // oMi[body].translation() by Link: the universe at the origin, then bodies 0..11 (what
+    // get_link_position's TODO would read from m_data, pinocchio_dynamics.hpp:181-192)
+    for (int r = 0; r < 3; r++) P.link[0][r] = 0.0;
+    for (int i = 0; i < FR_NB; i++)
+        for (int r = 0; r < 3; r++) P.link[1 + i][r] = B.p[i][r];
 }
 
 __device__ void set_state(const DevModel &M, DevPinocchio &P, const double *x, double time)
@@ -400,10 +405,12 @@ __global__ __launch_bounds__(64) void fr_object_kernel(ObjArgs a)
             }
         r[FR_NREC - 1] = 0.0;
         double t[7] = {0, 0, 0, 0, 0, 0, 0}, cost;
+        // kinematic link-position model: the sphere links' cached positions (PIVOT .. PANDA_LINK7)
+        const double (*lp)[3] = a.link_positions ? P.link + SC_LINK0 : nullptr;
         if (a.cost.kind == MPPI_COST_TRACK_POINT) {
-            cost = mppi_cost::track_point_cost(a.cost, r, P.state[2]);
+            cost = lp ? mppi_cost::track_point_cost<true>(a.cost, r, P.state[2], lp) : mppi_cost::track_point_cost(a.cost, r, P.state[2]);
         } else {
-            mppi_cost::assisted_manipulation_terms(a.cost, a.sc, r, P.state[2], t);
+            mppi_cost::assisted_manipulation_terms(a.cost, a.sc, r, P.state[2], t, lp);
             cost = 0.0;   // get_cost's running sum, term order (assisted_manipulation.cpp:48-71)
             for (int k = 0; k < 7; k++) cost += t[k];
         }

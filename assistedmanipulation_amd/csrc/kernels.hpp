@@ -154,6 +154,11 @@ struct FrRolloutArgs {
     // the rows after their horizon loops (fr_coop.hip launch_costs) instead of fr_step_cost_kernel;
     // stats as in FrCostArgs
     int costs_in_launch;
+    // the kinematic link-position model (mppi_set_link_positions): the launches' objective evaluates
+    // the self-collision term on each record's link positions (fr_coop.hip's *_lp_kernel; read by
+    // the host's launch selection only).  In the padding behind costs_in_launch: the argument
+    // block's size and every other offset stay what the default mode's kernels were built for.
+    int link_positions;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
     // this buffer (fr_coop.hip tail_draws; null: none): rank_draw_kernel then draws only the rest
@@ -231,6 +236,11 @@ struct FrCostArgs {
     const StepConst *fsteps;
     double *fcost;
     CostStats *stats;         // the update's rollout costs (not filter()'s) folded in, or null
+    // the kinematic link-position model (mppi_set_link_positions): the self-collision term from the
+    // records' link positions, which the objective rebuilds with the model and the rollout's dt
+    int link_positions;
+    const DevModel *model;
+    double dt;
 };
 
 struct PmRolloutArgs {
@@ -352,6 +362,7 @@ struct DevPinocchio {
     double state[MAX_X];                               // m_state (X = 31 used)
     double ee[MPPI_EE_N];                              // m_end_effector_state (mppi_amd.h MPPI_EE_*)
     double am[3], pad1;                                // the arm-mount frame position (the cost's workspace term)
+    double link[FR_LINKS][3];                          // oMi translations of the last calculate(), by Link (row 0: the universe)
 };
 enum ObjOp : int { OBJ_SET_STATE = 0, OBJ_STEP = 1, OBJ_FORECAST = 2, OBJ_COST = 3 };
 struct ObjArgs {
@@ -366,6 +377,7 @@ struct ObjArgs {
     double *out;          // forecast: [steps][MPPI_DF_N]; cost: [8] total + terms
     DevCost cost;         // cost: the objective
     StepConst sc;         // cost: trajectory_cost's constants of the wrench at `time`
+    int link_positions;   // cost: the self-collision term on the object's cached link positions (kinematic model)
 };
 hipError_t launch_fr_object(const ObjArgs &a, hipStream_t s);
 // forecast(t0 + k dt) for k < steps into out[steps][6] (mppi_forecast_table)
@@ -425,8 +437,9 @@ struct PmFusedArgs {
 constexpr int PM_STAMPS = 12;
 hipError_t launch_pm_update(const PmFusedArgs &a, hipStream_t s);
 // AssistedManipulation's seven per-term totals of one rollout from its [H][FR_REC] records
+// link_model: the kinematic link-position model's (else null: the zero stub's constant), dt the rollouts'
 hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const double *rec, int H, bool compact, double *out7,
-                           hipStream_t s);
+                           hipStream_t s, const DevModel *link_model = nullptr, double dt = 0.0);
 
 
 }  // namespace mppi_eng

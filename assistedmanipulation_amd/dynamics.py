@@ -54,13 +54,18 @@ class PinocchioDynamicsObject:
     STATE_DOF = abi.MPPI_FR_STATE
     CONTROL_DOF = abi.MPPI_FR_CONTROL
 
-    def __init__(self, handle, descriptor):
+    def __init__(self, handle, descriptor, link_positions=None):
         self._L = load()
         self._h = handle
         self._desc = descriptor
+        self._link_positions = link_positions
+        if link_positions is not None:
+            self.set_link_positions(abi.MPPI_LINK_POSITIONS_KINEMATIC if link_positions else abi.MPPI_LINK_POSITIONS_ZERO)
 
     @staticmethod
-    def create(initial_state, model=None, device=0):
+    def create(initial_state, model=None, device=0, link_positions=None):
+        """`link_positions`: True the kinematic link-position model, False the reference's stub,
+        None what MPPI_LINK_POSITIONS says (unset: the stub)."""
         from .trajectory import EngineError, FrankaRidgebackDynamics
         L = load()
         desc = FrankaRidgebackDynamics(model).descriptor()
@@ -71,7 +76,7 @@ class PinocchioDynamicsObject:
         st = L.mppi_dynamics_create(C.byref(desc), _p(x), int(device), C.byref(h))
         if st != abi.MPPI_OK:
             raise EngineError(st, L.mppi_last_error(None).decode())
-        return PinocchioDynamicsObject(h, desc)
+        return PinocchioDynamicsObject(h, desc, link_positions)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -95,7 +100,7 @@ class PinocchioDynamicsObject:
 
     def copy(self):
         """mppi::Dynamics::copy (mppi.hpp:47): a new object at this one's state."""
-        return PinocchioDynamicsObject.create(self.get_state())
+        return PinocchioDynamicsObject.create(self.get_state(), link_positions=self._link_positions)
 
     def set_state(self, state, time):
         x = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
@@ -123,6 +128,22 @@ class PinocchioDynamicsObject:
 
     def get_end_effector_state(self):
         return EndEffectorState.from_row(self.get_end_effector_state_row())
+
+    def set_link_positions(self, mode):
+        """mppi_dynamics_set_link_positions (abi.MPPI_LINK_POSITIONS_*); evaluate_cost follows it."""
+        self._check(self._L.mppi_dynamics_set_link_positions(self._h, int(mode)))
+        self._link_positions = int(mode) == abi.MPPI_LINK_POSITIONS_KINEMATIC
+
+    def link_positions(self):
+        """get_link_position of every Link (abi.LINK_NAMES order) after the last call, (13, 3): the
+        body frames' world translations of the last calculate() in the kinematic model, zeros in
+        the reference's stub."""
+        o = np.zeros((abi.MPPI_LINK_N, 3))
+        self._check(self._L.mppi_dynamics_link_positions(self._h, _p(o)))
+        return o
+
+    def get_link_position(self, link):
+        return self.link_positions()[int(link)]
 
     def query_row(self):
         """The members after the last call as MPPI_DYNAMICS_QUERY_N doubles."""

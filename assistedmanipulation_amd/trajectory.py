@@ -64,15 +64,20 @@ class Cost:
 
 class FrankaRidgebackDynamics(Dynamics):
     """FrankaRidgeback::PinocchioDynamics (pinocchio_dynamics.{hpp,cpp}).  `model` is a
-    mppi_frankaridgeback_desc; by default the body table generated from robot.urdf."""
+    mppi_frankaridgeback_desc; by default the body table generated from robot.urdf.
+    `link_positions`: what get_link_position answers in the rollouts (mppi_set_link_positions) -
+    True the kinematic model (the links' body-frame translations of the last calculate(), a live
+    self-collision term), False the reference's stub (zeros), None what MPPI_LINK_POSITIONS says
+    (unset: the stub)."""
     control_dof = abi.MPPI_FR_CONTROL
     state_dof = abi.MPPI_FR_STATE
 
-    def __init__(self, model=None):
+    def __init__(self, model=None, link_positions=None):
         if model is None:
             model = abi.mppi_frankaridgeback_desc()
             load().mppi_default_frankaridgeback(C.byref(model))
         self.model = model
+        self.link_positions = None if link_positions is None else bool(link_positions)
 
     def descriptor(self):
         d = abi.mppi_dynamics_desc()
@@ -208,7 +213,11 @@ class Trajectory:
         if st != abi.MPPI_OK:
             print(L.mppi_last_error(None).decode(), file=sys.stderr)
             return None
-        return Trajectory(h, configuration, dynamics, cost)
+        t = Trajectory(h, configuration, dynamics, cost)
+        lp = getattr(dynamics, "link_positions", None)
+        if lp is not None:   # FrankaRidgebackDynamics(link_positions=...)
+            t.set_link_positions(abi.MPPI_LINK_POSITIONS_KINEMATIC if lp else abi.MPPI_LINK_POSITIONS_ZERO)
+        return t
 
     # -- lifecycle --------------------------------------------------------------------------
     def close(self):
@@ -242,6 +251,22 @@ class Trajectory:
         self._check(self._L.mppi_set_shard(self._h, world, rank))
 
     # -- parity hooks ------------------------------------------------------------------------
+    def set_link_positions(self, mode):
+        """mppi_set_link_positions: abi.MPPI_LINK_POSITIONS_*; FrankaRidgeback handles, before the
+        first update."""
+        self._check(self._L.mppi_set_link_positions(self._h, int(mode)))
+
+    @property
+    def link_positions(self):
+        """Whether the rollouts use the kinematic link-position model (read-only; False for a
+        handle without links)."""
+        m = C.c_int(0)
+        st = self._L.mppi_get_link_positions(self._h, C.byref(m))
+        if st == abi.MPPI_ERR_UNSUPPORTED:
+            return False
+        self._check(st)
+        return m.value == abi.MPPI_LINK_POSITIONS_KINEMATIC
+
     def set_noise_source(self, source, seed=0x5EED):
         self._check(self._L.mppi_set_noise_source(self._h, int(source), int(seed)))
 

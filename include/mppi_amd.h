@@ -335,6 +335,42 @@ mppi_status mppi_update(mppi_handle *h, const double *state, double time);
 mppi_status mppi_set_graph(mppi_handle *h, int enable);
 mppi_status mppi_graph_updates(mppi_handle *h, int64_t *count);
 
+/* FrankaRidgeback::Link (frankaridgeback/dynamics.hpp:65-80), in the enum's order: the universe,
+ * then the bodies of the model descriptor (link L >= 1 is body L - 1).  mppi_link_name: the
+ * reference's LINK_NAMES (dynamics.cpp:42-56); host only, NULL out of range. */
+#define MPPI_LINK_OMNI_BASE_ROOT_LINK 0
+#define MPPI_LINK_X_SLIDER 1
+#define MPPI_LINK_Y_SLIDER 2
+#define MPPI_LINK_PIVOT 3
+#define MPPI_LINK_PANDA_LINK1 4
+#define MPPI_LINK_PANDA_LINK2 5
+#define MPPI_LINK_PANDA_LINK3 6
+#define MPPI_LINK_PANDA_LINK4 7
+#define MPPI_LINK_PANDA_LINK5 8
+#define MPPI_LINK_PANDA_LINK6 9
+#define MPPI_LINK_PANDA_LINK7 10
+#define MPPI_LINK_PANDA_LEFTFINGER 11
+#define MPPI_LINK_PANDA_RIGHTFINGER 12
+#define MPPI_LINK_N 13
+const char *mppi_link_name(int link);
+
+/* What Dynamics::get_link_position(Link) answers (the spheres of both objectives'
+ * self_collision_cost).  ZERO (the default): the reference's PinocchioDynamics stub,
+ * Vector3d::Zero() for every link (pinocchio_dynamics.hpp:181-192), so the term is a constant of
+ * the configuration.  KINEMATIC: the world translation of the link's body frame at the last
+ * calculate(), oMi[body].translation() - it lags the state by one step exactly as the end-effector
+ * position does: the cost of step k sees the links at q_0 for k = 0 and at q_{k-1} after.
+ * mppi_set_link_positions: FrankaRidgeback handles only (MPPI_ERR_UNSUPPORTED otherwise), before
+ * the first update (MPPI_ERR_INVALID after it, and for an unknown mode).  The environment variable
+ * MPPI_LINK_POSITIONS=1 (or 0; anything else fails the create with MPPI_ERR_INVALID) sets the mode
+ * new handles and dynamics objects start in.  Sharded handles take the mode per handle: every rank
+ * must set the same one.  These functions came after ABI version 5 without a version change (no
+ * struct changed): detect them by symbol. */
+#define MPPI_LINK_POSITIONS_ZERO 0
+#define MPPI_LINK_POSITIONS_KINEMATIC 1
+mppi_status mppi_set_link_positions(mppi_handle *h, int mode);
+mppi_status mppi_get_link_positions(mppi_handle *h, int *mode);
+
 /* Phase-split update for callers that run the collectives themselves (multi-GPU with an
  * external communicator, or two shards on one device in tests).  Between phase 1 and 2 the
  * caller all-reduces (sum) the R + 1 doubles of mppi_device_costs(h) - the R costs and slot R,
@@ -516,6 +552,11 @@ mppi_status mppi_dynamics_forecast(mppi_dynamics *d, const double *state, double
  * AssistedManipulation terms (MPPI_TERM_*; zeros for TrackPoint) = 8 doubles. */
 mppi_status mppi_cost_evaluate(const mppi_cost_desc *cost, mppi_dynamics *d, const double *state,
                                const double *control, const double *wrench6, double *out8);
+/* The object's link-position model (MPPI_LINK_POSITIONS_*; mppi_cost_evaluate follows it), and
+ * get_link_position of every Link after the object's last call: MPPI_LINK_N x 3 doubles, zeros in
+ * the zero mode. */
+mppi_status mppi_dynamics_set_link_positions(mppi_dynamics *d, int mode);
+mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out);
 /* forecast(t0 + k dt) for k < steps of the handle's attached forecast (steps x 6). */
 mppi_status mppi_forecast_table(mppi_handle *h, double t0, double dt, int64_t steps, double *out);
 

@@ -18,6 +18,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -119,6 +120,9 @@ class DeviceDynamics {
 public:
     virtual ~DeviceDynamics() = default;
     virtual bool describe(mppi_dynamics_desc &out) const = 0;
+    // the link-position model the rollouts of a trajectory on this dynamics use
+    // (MPPI_LINK_POSITIONS_*), or -1: the handle's own (the stub, or what MPPI_LINK_POSITIONS says)
+    virtual int link_positions() const { return -1; }
 };
 class DeviceCost {
 public:
@@ -205,10 +209,21 @@ public:
             std::cerr << mppi_last_error(nullptr) << std::endl;   // the reference prints and returns nullptr
             return nullptr;
         }
+        if (ddev->link_positions() >= 0 && mppi_set_link_positions(h, ddev->link_positions()) != MPPI_OK) {
+            std::cerr << mppi_last_error(nullptr) << std::endl;
+            mppi_destroy(h);
+            return nullptr;
+        }
         return std::unique_ptr<Trajectory>(new Trajectory(h, configuration, std::move(dynamics), std::move(cost)));
     }
 
     ~Trajectory() { mppi_destroy(m_h); }
+    // whether the rollouts use the kinematic link-position model (mppi_get_link_positions)
+    bool link_positions() const
+    {
+        int mode = MPPI_LINK_POSITIONS_ZERO;
+        return mppi_get_link_positions(m_h, &mode) == MPPI_OK && mode == MPPI_LINK_POSITIONS_KINEMATIC;
+    }
     Trajectory(const Trajectory &) = delete;
     Trajectory &operator=(const Trajectory &) = delete;
 
@@ -369,6 +384,25 @@ struct EndEffectorState {
     }
 };
 
+// FrankaRidgeback::Link (dynamics.hpp:65-80): the universe, then the model's bodies in order
+enum class Link {
+    OMNI_BASE_ROOT_LINK = MPPI_LINK_OMNI_BASE_ROOT_LINK,
+    X_SLIDER,
+    Y_SLIDER,
+    PIVOT,
+    PANDA_LINK1,
+    PANDA_LINK2,
+    PANDA_LINK3,
+    PANDA_LINK4,
+    PANDA_LINK5,
+    PANDA_LINK6,
+    PANDA_LINK7,
+    PANDA_LEFTFINGER,
+    PANDA_RIGHTFINGER,
+    _SIZE
+};
+static_assert((int)Link::_SIZE == MPPI_LINK_N && (int)Link::PANDA_RIGHTFINGER == MPPI_LINK_PANDA_RIGHTFINGER, "Link enum");
+
 // FrankaRidgeback::PinocchioDynamics (pinocchio_dynamics.hpp:30-427).  The rollouts evaluate the
 // body table (describe(): generated from robot.urdf by default); the object itself, when its
 // methods are called, is a device object (mppi_dynamics_*) created at the first call with the
@@ -378,6 +412,11 @@ public:
     struct Configuration {
         std::vector<double> initial_state;   // State (31); HUDDLED when empty
         int device = 0;
+        // the kinematic link-position model (mppi_set_link_positions): get_link_position answers
+        // the links' body-frame positions of the last calculate(), here and in the rollouts of a
+        // Trajectory created on this dynamics.  false: the handle's default (the reference's stub,
+        // zeros, unless MPPI_LINK_POSITIONS=1)
+        bool link_positions = false;
     };
     // wrench forecast(time) of the dynamics' forecast handle (DynamicsForecast::Handle), or none
     using WrenchSource = std::function<bool(double time, double *wrench6)>;
@@ -433,6 +472,16 @@ public:
         check(mppi_dynamics_end_effector(object(), r));
         return EndEffectorState::from_row(r);
     }
+    // get_link_position (dynamics.hpp:464; the reference's plugin answers zeros, .hpp:181-192)
+    std::array<double, 3> get_link_position(Link link)
+    {
+        double p[3 * MPPI_LINK_N];
+        check(mppi_dynamics_link_positions(object(), p));
+        const int l = (int)link;
+        if (l < 0 || l >= MPPI_LINK_N) throw std::out_of_range("link");
+        return {p[3 * l], p[3 * l + 1], p[3 * l + 2]};
+    }
+    int link_positions() const override { return m_configuration.link_positions ? MPPI_LINK_POSITIONS_KINEMATIC : -1; }
     std::vector<double> get_joint_position() { return query(0, 12); }
     std::vector<double> get_joint_velocity() { return query(12, 12); }
     std::vector<double> get_joint_acceleration() { return query(24, 12); }
@@ -455,6 +504,7 @@ public:
             mppi_dynamics_desc d;
             describe(d);
             check(mppi_dynamics_create(&d, x0.data(), m_configuration.device, &m_obj));
+            if (m_configuration.link_positions) check(mppi_dynamics_set_link_positions(m_obj, MPPI_LINK_POSITIONS_KINEMATIC));
         }
         return m_obj;
     }
