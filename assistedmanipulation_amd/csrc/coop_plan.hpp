@@ -14,6 +14,8 @@ namespace mppi_eng {
 struct EnvSwitches {
     bool draw_ahead_off, tail_draws_off, pm_fused_off, costs_in_launch_off, handover_off, split_off, stream_prio_off;
     int relay_k;   // MPPI_RELAY_K: workgroups the rows left over travel through (1..RELAY_K_MAX; 0: the default)
+    // MPPI_STAGE_WORK=0: a later relay member's stage waves do no objective work before their stage
+    bool stage_work_off;
     // the handle's device: its CU count (the rollout launches' rounds of workgroups) and LDS per
     // block (the fused point mass's residency check), set at create for that device - per handle, so
     // that handles created on different devices from several threads never read each other's

@@ -43,8 +43,20 @@ EnvSwitches env_switches_read()
     e.handover_off = is("MPPI_HANDOVER", '0');
     e.split_off = is("MPPI_SPLIT", '0');
     e.stream_prio_off = is("MPPI_STREAM_PRIO", '0');
-    const char *rk = std::getenv("MPPI_RELAY_K");
-    e.relay_k = (rk && rk[0] >= '1' && rk[0] <= '0' + RELAY_K_MAX) ? rk[0] - '0' : 0;
+    // the whole string must be decimal digits ("10" is not 1, no sign, no blank): anything else, or a
+    // value out of range, is not taken
+    auto whole = [](const char *name, long lo, long hi, long dflt) {
+        const char *v = std::getenv(name);
+        if (!v || !v[0]) return dflt;
+        long x = 0;
+        for (const char *c = v; *c; c++) {
+            if (*c < '0' || *c > '9' || x > hi) return dflt;
+            x = 10 * x + (*c - '0');
+        }
+        return (x >= lo && x <= hi) ? x : dflt;
+    };
+    e.relay_k = (int)whole("MPPI_RELAY_K", 1, RELAY_K_MAX, 0);
+    e.stage_work_off = is("MPPI_STAGE_WORK", '0');
     return e;
 }
 }  // namespace mppi_eng
@@ -1157,7 +1169,7 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
     // zero-fills above run on the null stream, which the non-blocking streams do not wait for.
     CREATE_TRY(hipDeviceSynchronize());
     CREATE_TRY(launch_rank(h->d_costs, h->S, h->d_rank, h->d_rank_keys, h->stream));
-    if (!h->trace_path.empty()) CREATE_TRY(dalloc(h, &h->d_trace, (size_t)(4 * ((h->R + 1) / 4 + 40))));   // + the relay waves' and block 0's chunks' slots (COOP_TRACE)
+    if (!h->trace_path.empty()) CREATE_TRY(dalloc(h, &h->d_trace, (size_t)(4 * ((h->R + 1) / 4 + FR_TRACE_EXTRA))));   // + the relay waves' and the relay hosts' tasks' slots (COOP_TRACE)
 #undef CREATE_TRY
     *out = h;
     return MPPI_OK;
@@ -1731,6 +1743,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         a.rec = h->d_rec;
         a.rx = h->d_rx;
         a.rtoken = ++h->relay_token ? h->relay_token : ++h->relay_token;   // (never 0)
+        a.stage_work = h->env.stage_work_off ? 0 : 1;
         a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
         // sharded: this rank's wait timeouts into cost slot R, which the all-reduce carries to every rank
         a.wait_sum = h->comm ? h->d_costs_local + h->R : (sharded(h) ? h->d_costs + h->R : nullptr);
@@ -1776,6 +1789,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         h->info[MPPI_INFO_SAMPLING] = ahead ? 2 : 0;
         h->info[MPPI_INFO_ROWS] = h->count + (folded ? 1 : 0);
         h->info[MPPI_INFO_HANDOVER] = plan.x_kernel ? -2 : -1;   // -2: read from the device on request
+        h->info[MPPI_INFO_STAGE_WORK] = plan.x_kernel ? -2 : 0;   // -2: read from the device on request
         if (folded) h->opt_rec_compact = false;   // the folded row: fr_coop_x_kernel's 768-B records
         if (folded) {   // the optimal cost is ready with this update's rollouts; phase 3's host block
                         // carries it back (finish_kernel copies d_opt), on the same stream
@@ -2005,7 +2019,7 @@ static mppi_status phase3_wait(mppi_handle *h, double seq)
         std::memcpy(h->U_host.data(), h->h_out, (size_t)HC * sizeof(double));
     }
     if (h->d_trace) {   // diagnostics: append this update's per-block records
-        std::vector<uint32_t> tr((size_t)(4 * ((h->R + 1) / 4 + 40)));
+        std::vector<uint32_t> tr((size_t)(4 * ((h->R + 1) / 4 + FR_TRACE_EXTRA)));
         HIP_TRY(hipMemcpy(tr.data(), h->d_trace, tr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (FILE *fp = std::fopen(h->trace_path.c_str(), "ab")) {
             std::fwrite(tr.data(), sizeof(uint32_t), tr.size(), fp);
@@ -2631,6 +2645,12 @@ mppi_status mppi_update_info(mppi_handle *h, int64_t *info, int n)
         HIP_TRY(hipStreamSynchronize(h->stream));
         HIP_TRY(hipMemcpy(&w, &h->d_status->handover, sizeof(w), hipMemcpyDeviceToHost));
         h->info[MPPI_INFO_HANDOVER] = w;
+    }
+    if (n > MPPI_INFO_STAGE_WORK && h->info[MPPI_INFO_STAGE_WORK] == -2) {   // the launches' count since create
+        int w = 0;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(&w, &h->d_status->ahead_chunks, sizeof(w), hipMemcpyDeviceToHost));
+        h->info[MPPI_INFO_STAGE_WORK] = w;
     }
     h->info[MPPI_INFO_WAIT_TIMEOUTS_TOTAL] = h->wait_timeouts_total;
     h->info[MPPI_INFO_GRAPH_UPDATES] = h->graph_updates;

@@ -1786,6 +1786,11 @@ __device__ __forceinline__ bool row_live(const FrRolloutArgs &a, int64_t lr)
 // LDS words (Lq): the main waves' steps, the groups' next chunk to take and chunks completed, the
 // relay's stage
 enum { Q_PROG = 0, Q_NEXT = 4, Q_DONE = 9, Q_STAGE = 14, Q_N = 16 };
+// COST_TRACE slots past the main waves' (4 gridDim.x): 0 the relay rows, 1.. the members' stages, 16.. unused
+// (block 0's chunks until r06), then per traced relay host (group 0's first and last member)
+// 8 chunks x 5 groups, the relay group's closing and the ends of waves 4 .. 7
+constexpr int TR_HOSTS = 40, TR_HOST_N = 44;
+static_assert(TR_HOSTS + 2 * TR_HOST_N <= FR_TRACE_EXTRA, "trace buffer (engine.cpp)");
 // LDS flags (Lflag): main wave g's records are stored (g), the relay's rows are done (LF_RELAY),
 // main wave g's kept columns are copied (LF_KEPT + g: its rows' previous eps is read, so their next
 // draws may overwrite it)
@@ -1840,31 +1845,13 @@ __device__ __forceinline__ bool chunk_ready(const FrRolloutArgs &a, int g, int c
     return lds_read(Lflag + g) != 0;
 }
 
-// The step costs of chunk c of group g into Lcs; the pass that completes the group sums its rows
-template <int CK, bool EN, bool LP>
-__device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c, int lane, const double *Lmodel, double *Lcs,
-                                          int *Lq)
+// A chunk's step costs are in Lcs: count it, and the pass that completes the group sums its rows
+__device__ __forceinline__ void chunk_done(const FrRolloutArgs &a, int g, int lane, double *Lcs, int *Lq)
 {
     const int H = a.H;
     int cb, ce;
     group_chunks(a, g, cb, ce);   // the group's chunks in this workgroup
-    const int i = lane >> 4, k = c * CH + (lane & 15);
-    const int64_t lr0 = group_row0(a, g), lr = lr0 + i;
-    const bool rl = row_live(a, lr), live = rl && k < H;
-    const bool frow = a.fcost != nullptr && lr == a.count;
-    const int64_t lrv = rl ? lr : lr0;   // any live row's records when unused
-    const double *rec = frow ? a.frec : a.rec + lrv * H * FR_REC;
-    const StepConst *stp = frow ? a.fsteps : a.steps;
-    const int kk = live ? k : 0;
-    PMARK(8);
-    double cs;
-    if constexpr (LP)
-        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO,
-                                                                     mppi_cost::LinkModel{a.model, a.dt}, kk == 0);
-    else
-        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2>(*a.cost, stp[kk], rec + (int64_t)kk * FR_REC, Lmodel + T_LO);
-    PMARK_D(9, cs);
-    if (live) Lcs[(g * ROWS_PER_WAVE + i) * HC_MAX + k] = cs;
+    const int64_t lr0 = group_row0(a, g);
     // the stores before the count: the wave that completes the group reads every chunk's costs
     const int n = __builtin_amdgcn_readfirstlane(
         __hip_atomic_fetch_add(Lq + Q_DONE + g, lane == 0 ? 1 : 0, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -1875,11 +1862,20 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
     const bool from_prev = g == 4 && a.relay_k > 1 && m > 0;
     const bool to_next = g == 4 && a.relay_k > 1 && m + 1 < a.relay_k;
     RelayXfer *x = (from_prev || to_next) ? a.rx + ((int)blockIdx.x % RELAY_STRIDE) : nullptr;
+#ifdef COST_TRACE   // the relay group's closing in the last member's host: entry, token, sums, store
+    uint32_t *trc = nullptr;
+    if (a.trace && g == 4 && !to_next && (int)blockIdx.x % RELAY_STRIDE == 0 && lane == 0)
+        trc = a.trace + 4 * (gridDim.x * 4 + TR_HOSTS + (from_prev ? 1 : 0) * TR_HOST_N + 40);
+    if (trc) trc[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
     double J0 = 0.0;
     if (from_prev) {   // bounded; on a timeout the update fails (wait_timeouts)
         const bool ok = wait_token(a, &x->sums_tok[m - 1][0]);
         J0 = (ok && lane < ROWS_PER_WAVE) ? __hip_atomic_load(&x->sums[m - 1][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     }
+#ifdef COST_TRACE
+    if (trc) trc[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
     if (lane < ROWS_PER_WAVE) {
         const int64_t r = lr0 + lane;
         if (row_live(a, r) || to_next) {
@@ -1902,6 +1898,9 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
                 for (int u = 0; u < 16; u++) J += c[u];
             }
             for (; q < Hend; q++) J += cr[q];
+#ifdef COST_TRACE
+            if (trc) trc[2] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
             if (to_next) {   // the next member continues from these (sc1, then the token)
                 __hip_atomic_store(&x->sums[m][lane], J, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __builtin_amdgcn_s_waitcnt(0);
@@ -1915,19 +1914,86 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
                 a.cost_out[a.begin + r] = J;
                 mppi_cost::fold_cost_stats(a.stats, J, r);
             }
+#ifdef COST_TRACE
+            if (trc) {
+                __builtin_amdgcn_s_waitcnt(0);
+                trc[3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+            }
+#endif
         }
     }
 }
 
+// What lane (row i, step k) of chunk c of group g evaluates: the record, its step constants, the
+// slot of its cost in Lcs (live: the row and the step exist)
+struct ChunkLane {
+    const double *rec;
+    const StepConst *stp;
+    int kk, slot;
+    bool live;
+};
+__device__ __forceinline__ ChunkLane chunk_lane(const FrRolloutArgs &a, int g, int c, int lane)
+{
+    const int H = a.H;
+    const int i = lane >> 4, k = c * CH + (lane & 15);
+    const int64_t lr0 = group_row0(a, g), lr = lr0 + i;
+    const bool rl = row_live(a, lr), live = rl && k < H;
+    const bool frow = a.fcost != nullptr && lr == a.count;
+    const int64_t lrv = rl ? lr : lr0;   // any live row's records when unused
+    const int kk = live ? k : 0;
+    ChunkLane L;
+    L.rec = (frow ? a.frec : a.rec + lrv * H * FR_REC) + (int64_t)kk * FR_REC;
+    L.stp = (frow ? a.fsteps : a.steps) + kk;
+    L.kk = kk;
+    L.slot = (g * ROWS_PER_WAVE + i) * HC_MAX + k;
+    L.live = live;
+    return L;
+}
+
+// The step costs of chunk c of group g into Lcs; the pass that completes the group sums its rows.
+// The kernel's code has to stay inside the 64-KB instruction cache: a build that held a second copy
+// of the objective (81 KB against the parent's 62) ran every step loop 7 % slower, whether or not the
+// copy ever ran.  cost_work has two call sites and no more.
+template <int CK, bool EN, bool LP>
+__device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c, int lane, const double *Lmodel, double *Lcs,
+                                          int *Lq)
+{
+    const ChunkLane L = chunk_lane(a, g, c, lane);
+    PMARK(8);
+    double cs;
+    if constexpr (LP)
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
+                                                                     mppi_cost::LinkModel{a.model, a.dt}, L.kk == 0);
+    else
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2>(*a.cost, *L.stp, L.rec, Lmodel + T_LO);
+    PMARK_D(9, cs);
+    if (L.live) Lcs[L.slot] = cs;
+    chunk_done(a, g, lane, Lcs, Lq);
+}
+
+// The instantiations whose relay stage waves take chunks ahead of their stage (the kernel body)
+template <int CK, bool EN>
+constexpr bool STAGE_AHEAD = CK == CK_ASSISTED_MANIPULATION && !EN;
+
 // A wave's objective work: chunks of any group, its own group (first) first, each taken from the
 // group's counter when it is ready (a chunk taken just as another wave took the one before it
 // waits for its records); returns once every chunk is taken.  Bounded.
+// until: a relay stage's wave ahead of its stage (its stage s >= 1 of a member m >= 1, the kernel
+// body) takes no further chunk once the stage before its own runs - stage s - 2 has signalled, or
+// for s = 1 the previous member's state has arrived - so that a chunk in hand ends within that
+// stage's steps (16 us at 4096 x 64 against 12-14 for a pass beside a main wave), and returns.
+// Such a wave takes only a chunk it has seen ready, and counts it (Status::ahead_chunks).
 template <int CK, bool EN, bool LP>
 __device__ __forceinline__ void cost_work(const FrRolloutArgs &a, int first, int ng, int lane, const double *Lmodel,
-                                         double *Lcs, int *Lflag, int *Lq)
+                                         double *Lcs, int *Lflag, int *Lq, int until = 0)
 {
 #pragma unroll 1
     for (int spin = 0; spin < WAIT_SPINS; spin++) {
+        if (until >= 2 && lds_read(Lq + Q_STAGE) >= until - 1) return;
+        if (until == 1 && __builtin_amdgcn_readfirstlane(__hip_atomic_load(
+                &a.rx[(int)blockIdx.x % RELAY_STRIDE].state_tok[(int)blockIdx.x / RELAY_STRIDE - 1][0], __ATOMIC_RELAXED,
+                __HIP_MEMORY_SCOPE_AGENT)) == a.rtoken)
+            return;
         bool left = false, did = false;
 #pragma unroll 1
         for (int d = 0; d < ng && !did; d++) {
@@ -1938,9 +2004,22 @@ __device__ __forceinline__ void cost_work(const FrRolloutArgs &a, int first, int
             if (c0 >= nch) continue;
             left = true;
             if (!chunk_ready(a, g, c0, Lflag, Lq)) continue;
-            // every lane executes the add (lane 0 adds 1): no lane-dependent branch around it
-            const int c = __builtin_amdgcn_readfirstlane(
-                __hip_atomic_fetch_add(Lq + Q_NEXT + g, lane == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            int c;
+            if (until) {
+                // ahead of a relay stage: the chunk seen ready or none (a compare-and-swap, lane 0's; the
+                // other lanes' expected value never matches) - a chunk claimed past it would have to be
+                // waited for while the relay's chain waits for this wave
+                int expect = lane == 0 ? c0 : -2;
+                const bool won = __hip_atomic_compare_exchange_strong(Lq + Q_NEXT + g, &expect, c0 + 1, __ATOMIC_RELAXED,
+                                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (!__builtin_amdgcn_readfirstlane((int)won)) continue;
+                c = c0;
+                if (lane == 0 && a.status) atomicAdd(&const_cast<Status *>(a.status)->ahead_chunks, 1);
+            } else {
+                // every lane executes the add (lane 0 adds 1): no lane-dependent branch around it
+                c = __builtin_amdgcn_readfirstlane(
+                    __hip_atomic_fetch_add(Lq + Q_NEXT + g, lane == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            }
             if (c >= nch) continue;
             int w = 0;
             while (!chunk_ready(a, g, c, Lflag, Lq) && w < WAIT_SPINS) {
@@ -1948,16 +2027,19 @@ __device__ __forceinline__ void cost_work(const FrRolloutArgs &a, int first, int
                 w++;
             }
             if (w == WAIT_SPINS && lane == 0) note_wait_timeout(a);
-#ifdef COST_TRACE   // block 0's chunks: start, end, wave (slots past the relay's)
+#ifdef COST_TRACE   // the relay hosts' chunks (group 0's first and last member): start, end, wave, chunk
             const uint32_t tc0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
             cost_chunk<CK, EN, LP>(a, g, c, lane, Lmodel, Lcs, Lq);
 #ifdef COST_TRACE
-            if (a.trace && blockIdx.x == 0 && lane == 0 && c < 4) {
-                uint32_t *tr = a.trace + 4 * (gridDim.x * 4 + 16 + 4 * g + c);
+            const int hm = (int)blockIdx.x / RELAY_STRIDE;
+            if (a.trace && (int)blockIdx.x % RELAY_STRIDE == 0 && (hm == 0 || hm == a.relay_k - 1) && hm < a.relay_k &&
+                lane == 0 && c - cb < 8) {
+                uint32_t *tr = a.trace + 4 * (gridDim.x * 4 + TR_HOSTS + (hm == 0 ? 0 : 1) * TR_HOST_N + 8 * g + (c - cb));
                 tr[0] = tc0;
                 tr[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
                 tr[2] = threadIdx.x >> 6;
+                tr[3] = (uint32_t)(c << 8 | (until ? 1 : 0));   // (1: taken ahead of the wave's relay stage)
             }
 #endif
             did = true;
@@ -2010,7 +2092,8 @@ __device__ __forceinline__ int relay_step(const FrRolloutArgs &a, int r, int H)
 // stage ran (false: the previous stage never signalled, counted in Status::wait_timeouts).
 template <int CK, bool EN>
 __device__ __forceinline__ bool relay_stage(const FrRolloutArgs &a, int s, int m, int lane, double *Lk, double *Lw,
-                                            const double *Lmodel, const double *Lx0, int *Lflag, int *Lq, double *Lst)
+                                            const double *Lmodel, const double *Lx0, int *Lflag, int *Lq, double *Lst,
+                                            bool drawn = false)
 {
     const int H = a.H;
     const int q = (int)blockIdx.x % RELAY_STRIDE;
@@ -2023,7 +2106,8 @@ __device__ __forceinline__ bool relay_stage(const FrRolloutArgs &a, int s, int m
         // rank_draw_kernel): first where the stage waits long for its turn (later members), after
         // the stage in member 0, whose stages follow each other within microseconds when the relay
         // spans several workgroups
-        if (m > 0 && a.ahead_noise) group_draws(a, s, lane, Lflag);
+        // (drawn: the kernel body made them, ahead of the objective chunks the wave took before its turn)
+        if (m > 0 && a.ahead_noise && !drawn) group_draws(a, s, lane, Lflag);
         __builtin_amdgcn_s_setprio(3);   // above the main waves (1) and the objective's (0)
         kb = relay_step(a, r, H);
         ke = relay_step(a, r + 1, H);

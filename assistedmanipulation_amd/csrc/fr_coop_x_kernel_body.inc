@@ -41,6 +41,12 @@
         }
     }
     const bool cil = a.costs_in_launch != 0;
+    // AssistedManipulation without the energy tank (STAGE_AHEAD, fr_coop.hip): a later relay member's
+    // stage waves take objective chunks ahead of their stage.  The objective's chunks then have two
+    // call sites (cost_work; each is a copy of the objective's code, and the kernel has to stay inside
+    // the 64-KB instruction cache, fr_coop.hip cost_chunk): those waves ahead of their stage, and every
+    // wave after its rows.  The tank's and TrackPoint's kernels keep a site per branch and no work
+    // ahead: joined, their relay step loops grew (TrackPoint's from 776 to 821 instructions).
     if (wv < 4) {
         if (cil) {   // the next draws for this wave's rows may now overwrite their previous eps
             __builtin_amdgcn_s_waitcnt(0);
@@ -53,18 +59,45 @@
         __builtin_amdgcn_s_setprio(0);
         if (cil) {
             signal_records(Lflag + wv);
-            cost_work<CK, EN, LP>(a, wv, ng, lane, Lmodel, Lcs, Lflag, Lq);
+            if constexpr (!STAGE_AHEAD<CK, EN>) cost_work<CK, EN, LP>(a, wv, ng, lane, Lmodel, Lcs, Lflag, Lq);
         }
-#ifdef COST_TRACE   // COOP_TRACE builds: slot 3 = the wave's end (after its objective work)
-        if (a.trace && lane == 0) a.trace[4 * wblk + 3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#endif
     } else {
         const int s = wv - 4;   // this wave's SIMD
         const bool relay = xr && (s == 0 || a.handover);
-        if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst);
+        if constexpr (STAGE_AHEAD<CK, EN>) {
+            // Stages 1 .. 3 of a later member wait 80-115 us of the launch for their turn.  Their
+            // workgroup's main waves store records all that time, and with nobody to evaluate them the
+            // member's host began its closing with ten passes in hand and ended 15 us after every
+            // other workgroup (profiles/launch_tail/).  These waves make their draws, take objective
+            // chunks until the stage before their own runs (cost_work's `until`), then run their stage.
+            const bool ahead = relay && cil && a.handover && a.stage_work && member > 0 && s > 0;
+            if (ahead) {
+                if (a.ahead_noise) group_draws(a, s, lane, Lflag);
+                cost_work<CK, EN, LP>(a, s, ng, lane, Lmodel, Lcs, Lflag, Lq, s);
+            }
+            if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst, ahead);
+        } else {
+            if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst);
+        }
         if (!cil) return;
         // the draws for main wave s's rows (relay stages made theirs before their stage; wave 0's
         // rows of a workgroup with rows left over are left to rank_draw_kernel)
         if (a.ahead_noise && !relay && !(member == 0 && s == 0)) group_draws(a, s, lane, Lflag);
-        cost_work<CK, EN, LP>(a, s, ng, lane, Lmodel, Lcs, Lflag, Lq);
+        if constexpr (!STAGE_AHEAD<CK, EN>) cost_work<CK, EN, LP>(a, s, ng, lane, Lmodel, Lcs, Lflag, Lq);
     }
+    if constexpr (STAGE_AHEAD<CK, EN>) {
+        if (cil) {
+            // (the lane opaque: what cost_work derives from it is otherwise formed ahead of the branches
+            // and lives across the step loops)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            cost_work<CK, EN, LP>(a, wv & 3, ng, ln, Lmodel, Lcs, Lflag, Lq);
+        }
+    }
+#ifdef COST_TRACE   // COOP_TRACE builds: slot 3 = the main wave's end (after its objective work); the traced
+                    // relay hosts (cost_work): the ends of waves 4 .. 7
+    if (a.trace && lane == 0 && wv < 4) a.trace[4 * (blockIdx.x * 4 + wv) + 3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+    if (a.trace && wv >= 4 && xr && lane == 0 && (int)blockIdx.x % RELAY_STRIDE == 0 && (member == 0 || member == a.relay_k - 1))
+        a.trace[4 * (gridDim.x * 4 + TR_HOSTS + (member == 0 ? 0 : 1) * TR_HOST_N + 41) + (wv - 4)] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
+

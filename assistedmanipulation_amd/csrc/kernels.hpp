@@ -19,7 +19,10 @@ struct Status {
     // fr_coop_x_kernel: bounded in-launch waits that gave up in this update's rollout launch (some
     // rows' costs were then never written): the finish kernels fail the update on it and reset it
     int wait_timeouts;
-    int pad[3];
+    // fr_coop_x_kernel: objective chunks that a later relay member's stage waves took ahead of their
+    // stage (cost_work's `until`), counted since create (mppi_update_info, MPPI_INFO_STAGE_WORK)
+    int ahead_chunks;
+    int pad[2];
     double minimum, maximum, total;   // total: the softmin normaliser, summed by the finish kernels
     double tsplit[8];           // its GRAD_SPLIT partial sums (weights_gradient_kernel)
 };
@@ -115,6 +118,7 @@ struct FinishArgs {
     double *wait_local;
 };
 
+constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
     const DevCost *cost;
@@ -132,6 +136,7 @@ struct FrRolloutArgs {
     int cost_kind;            // mppi_cost_kind: AssistedManipulation or TrackPoint
     int energy;               // AssistedManipulation enable_energy_limit: the tank's NLE power
     uint32_t *trace;          // diagnostics (COOP_TRACE builds, MPPI_WAVE_TRACE): per block start, end, hw id, xcc
+                              // (four words a slot: one per main wave, then FR_TRACE_EXTRA, fr_coop.hip TR_*)
     // filter() of the previous update folded into this launch as one extra row (fr_coop.hip):
     // its state, published U*, step constants and cost output
     const double *fx0, *fU;
@@ -172,6 +177,10 @@ struct FrRolloutArgs {
     // MPPI_DEBUG_* fault injection (mppi_debug_inject; 0 in production): bit 0, relay stage 1 of
     // the workgroup with rows left over never signals stage 2 (tests the wait-timeout failure)
     int debug;
+    // MPPI_STAGE_WORK (0: off): the waves of a later relay member's stages 1 .. 3 evaluate objective
+    // chunks until the stage before their own runs (fr_coop_x_kernel_body.inc).  In the padding
+    // behind debug.
+    int stage_work;
     // The relay over relay_k workgroups (fr_coop.hip relay_stage): member m of relay group q is
     // workgroup q + RELAY_STRIDE m and runs stages 4 m .. 4 m + 3 over its share of the horizon's
     // chunks; the lanes' state and the rows' partial cost sums cross between members through rx,

@@ -490,11 +490,14 @@ class Trajectory:
         sampling mode 0/1/2, rows rolled out, the step at which the fifth wave's rows moved off
         the doubled SIMD or -1, the in-launch waits that gave up in the last update - which then
         failed - and summed since create)."""
-        out = np.zeros(abi.MPPI_UPDATE_INFO_N, dtype=np.int64)
-        self._check(self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size))
         keys = ("cooperative", "folded_filter", "objective_in_launch", "tail_draws", "sampling", "rows", "handover",
                 "wait_timeouts", "wait_timeouts_total", "fused_update", "graph_updates", "graph_failures",
-                "update_count")
+                "update_count", "stage_work")
+        out = np.zeros(abi.MPPI_UPDATE_INFO_N, dtype=np.int64)
+        st = self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+        if st == abi.MPPI_ERR_INVALID:   # a library from before the stage_work slot takes one slot fewer
+            st = self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size - 1)
+        self._check(st)
         return {k: int(v) for k, v in zip(keys, out)}
 
     def debug_inject(self, fault, updates=1):

@@ -446,7 +446,10 @@ mppi_status mppi_dims(mppi_handle *h, int64_t *rollouts_R, int64_t *steps_H,
                                              its collectives matched; the handle stays eager) */
 #define MPPI_INFO_UPDATE_COUNT 12         /* successful updates since create (Trajectory::update
                                              calls that published, whichever entry made them) */
-#define MPPI_UPDATE_INFO_N 13
+#define MPPI_INFO_STAGE_WORK 13           /* objective chunks that a later relay member's stage waves evaluated ahead
+                                           * of their stage, counted on the device since create (0 with
+                                           * MPPI_STAGE_WORK=0, one relay member, the tank or TrackPoint) */
+#define MPPI_UPDATE_INFO_N 14
 mppi_status mppi_update_info(mppi_handle *h, int64_t *info, int n);
 
 /* Fault injection for the failure-detection tests (no reference counterpart; never set in

@@ -26,7 +26,8 @@
 #                      built by tools/ab_build.sh; "tree" = the in-tree library); BENCH_ARGS and
 #                      AB_ENV_<V> (extra env for variant V, e.g. AB_ENV_tree0="MPPI_HANDOVER=0") apply
 #   pmstamps[:VARIANT] the fused point-mass kernel's phase stamps (MPPI_PM_STAMPS=1), in-tree or a variant
-#   wtrace:VARIANT     per-wave trace of VARIANT's COOP_TRACE build (tools/wave_trace_r03.py)
+#   wtrace:VARIANT[:NAME]  per-wave trace of VARIANT's COOP_TRACE + COST_TRACE build (tools/wave_trace_tail.py;
+#                      WTRACE_K: the relay's members, default 2; AB_ENV_<NAME> applies) -> NAME_wave_trace.txt
 #   kpmc:V1,V2,..      PMC of the kernels outside the rollout launch (weights / finish / rank), per library
 # Output: gpurun_out/$TAG/.
 set -o pipefail
@@ -216,11 +217,14 @@ step_pmstamps() {   # [variant]: the fused point-mass kernel's phase stamps (MPP
 }
 
 
-step_wtrace() {   # variant
+step_wtrace() {   # variant [name]: AB_ENV_<name> (extra env, e.g. AB_ENV_off="MPPI_STAGE_WORK=0") applies
     local lib=$PWD/gpurun_variants/$1/libmppi_amd.so
-    MPPI_WAVE_TRACE=$PWD/$O/wt.bin MPPI_AMD_LIB=$lib timeout -k 10 120 python bench.py --steps 40 --warmup 10 \
-        --full --no-cpu-baseline $BENCH_ARGS > $O/wt.json 2> $O/wt.err || { echo "wtrace rc=$?"; tail $O/wt.err; return 1; }
-    python3 tools/wave_trace_r06.py $O/wt.bin 1064 | tee $O/wave_trace.txt
+    local n=${2:-wt}
+    local envv="AB_ENV_$n"
+    rm -f $O/$n.bin
+    env MPPI_WAVE_TRACE=$PWD/$O/$n.bin MPPI_AMD_LIB=$lib ${!envv} timeout -k 10 120 python bench.py --steps 40 --warmup 10 \
+        --full --no-cpu-baseline $BENCH_ARGS > $O/$n.json 2> $O/$n.err || { echo "wtrace rc=$?"; tail $O/$n.err; return 1; }
+    python3 tools/wave_trace_tail.py $O/$n.bin ${WTRACE_K:-2} > $O/${n}_wave_trace.txt && tail -14 $O/${n}_wave_trace.txt
 }
 
 for s in "$@"; do
@@ -242,7 +246,7 @@ for s in "$@"; do
         graphab) step_graphab "$arg" ;;
         absizes) step_absizes "${arg%%:*}" "$( [ "${arg#*:}" != "$arg" ] && echo ${arg#*:} )" ;;
         ab) step_ab "${arg%%:*}" "$( [ "${arg#*:}" != "$arg" ] && echo ${arg#*:} )" ;;
-        wtrace) step_wtrace "$arg" ;;
+        wtrace) step_wtrace "${arg%%:*}" "$( [ "${arg#*:}" != "$arg" ] && echo ${arg#*:} )" ;;
         pmstamps) step_pmstamps "$arg" ;;
         *) echo "unknown step $s"; exit 2 ;;
     esac || { echo "step $s failed"; exit 1; }
