@@ -15,7 +15,7 @@ from .config import (Configuration, Smoothing, average_forecast_configuration, c
                      frankaridgeback_configuration, huddled_state, kalman_forecast_configuration,
                      locf_forecast_configuration, point_mass_configuration)
 from .trajectory import (AssistedManipulation, Cost, Dynamics, EngineError, TrackPoint,  # noqa: E402
-                         FrankaRidgebackDynamics, PointMassDynamics, QuadraticCost, Trajectory,
+                         FrankaRidgebackDynamics, PointMassDynamics, Predicted, QuadraticCost, Trajectory,
                          comm_unique_id, shard_range)
 
 from .csvlog import MPPILogger  # noqa: E402
@@ -27,5 +27,5 @@ __all__ = [
     "huddled_state", "point_mass_configuration", "locf_forecast_configuration", "average_forecast_configuration",
     "kalman_forecast_configuration", "AssistedManipulation", "TrackPoint", "Cost", "Dynamics",
     "EngineError", "FrankaRidgebackDynamics", "PointMassDynamics", "QuadraticCost", "Trajectory",
-    "comm_unique_id", "shard_range",
+    "comm_unique_id", "shard_range", "Predicted",
 ]

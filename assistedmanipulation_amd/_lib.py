@@ -63,6 +63,8 @@ PROTOTYPES = {
     "mppi_optimal_cost": (C.c_int, [_h, _dp]),
     "mppi_argmin": (C.c_int, [_h, _i64p]),
     "mppi_optimal_terms": (C.c_int, [_h, _dp]),
+    "mppi_predicted_optimal": abi.PREDICTED_PROTOTYPES["mppi_predicted_optimal"],
+    "mppi_predicted_rollouts": abi.PREDICTED_PROTOTYPES["mppi_predicted_rollouts"],
     "mppi_update_duration": (C.c_int, [_h, _dp]),
     "mppi_update_last": (C.c_int, [_h, _dp]),
     "mppi_device_costs_count": (C.c_int64, [_h]),

@@ -59,6 +59,15 @@ LINK_NAMES = ("omni_base_root_link", "x_slider", "y_slider", "pivot", "panda_lin
               "panda_link4", "panda_link5", "panda_link6", "panda_link7", "panda_leftfinger", "panda_rightfinger")
 MPPI_LINK_POSITIONS_ZERO = 0
 MPPI_LINK_POSITIONS_KINEMATIC = 1
+# One row of mppi_predicted_optimal / mppi_predicted_rollouts (MPPI_PRED_*): q_k, qd_k, the tank level,
+# then the grasp-frame, arm-mount and link positions at q_k
+MPPI_PRED_Q, MPPI_PRED_QD, MPPI_PRED_ENERGY, MPPI_PRED_EE, MPPI_PRED_ARM_MOUNT, MPPI_PRED_LINKS = 0, 12, 24, 25, 28, 31
+MPPI_PRED_N = 70
+# (restype, argtypes) of the two calls, bound by _lib.load() with the rest of the header's functions
+PREDICTED_PROTOTYPES = {
+    "mppi_predicted_optimal": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mppi_predicted_rollouts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double)]),
+}
 TERM_NAMES = ("joint_limit", "self_collision", "workspace", "energy_tank", "joint_velocity", "trajectory",
               "manipulability")
 

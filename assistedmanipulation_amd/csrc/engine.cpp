@@ -28,6 +28,8 @@
 #include "../../include/mppi_amd_frankaridgeback.h"
 #include "engine_types.hpp"
 #include "kernels.hpp"
+#include "predict_plan.hpp"
+#include "fr_predict.hpp"
 
 using namespace mppi_eng;
 
@@ -248,6 +250,11 @@ struct mppi_handle {
     // mppi_debug_inject: fault bits for the next debug_updates rollout launches (tests only)
     int debug_flags = 0, debug_updates = 0;
     bool published_once = false;   // an update has published U* (and so has a filter() row)
+    // mppi_predicted_optimal / _rollouts: the requested rows' record addresses and the rows of
+    // MPPI_PRED_N doubles, allocated on first use and grown with n H (nothing on the update path)
+    PredictRow *d_pred_rows = nullptr;
+    double *d_pred_out = nullptr;
+    size_t pred_rows_cap = 0, pred_out_cap = 0;
     // the point mass in one launch per update (pm_fused.hip, launch_pm_update)
     DevPointMass pm_host{};
     unsigned *d_pm_sync = nullptr;   // [2] grid-barrier and ticket counters (monotonic)
@@ -2590,6 +2597,71 @@ mppi_status mppi_optimal_terms(mppi_handle *h, double *terms7)
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     std::memcpy(terms7, h->h_opt + 1, 7 * sizeof(double));
     return MPPI_OK;
+}
+
+// Predicted trajectories (fr_predict.hip): `rows` (host) address n rollouts' records in `rec`; the
+// kernel runs on `s`, one device-to-host copy follows, then a synchronise.  The buffers grow with
+// the request and stay with the handle.
+static mppi_status predicted_run(mppi_handle *h, const double *rec, const std::vector<PredictRow> &rows, hipStream_t s, double *out)
+{
+    const size_t n = rows.size(), doubles = n * (size_t)h->H * MPPI_PRED_N;
+    if (n > h->pred_rows_cap) {
+        dfree(h, h->d_pred_rows);
+        h->pred_rows_cap = 0;
+        HIP_TRY(dalloc(h, &h->d_pred_rows, n));
+        h->pred_rows_cap = n;
+    }
+    if (doubles > h->pred_out_cap) {
+        dfree(h, h->d_pred_out);
+        h->pred_out_cap = 0;
+        HIP_TRY(dalloc(h, &h->d_pred_out, doubles));
+        h->pred_out_cap = doubles;
+    }
+    const bool energy = h->cost_kind == MPPI_COST_ASSISTED_MANIPULATION && h->am.enable_energy_limit;   // phase 1's a.energy
+    // (the caller's `rows` outlive the synchronise below)
+    HIP_TRY(hipMemcpyAsync(h->d_pred_rows, rows.data(), n * sizeof(PredictRow), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_fr_predict(h->d_model, rec, h->d_pred_rows, (int64_t)n, (int)h->H, energy ? 1 : 0, h->d_pred_out, s));
+    HIP_TRY(hipMemcpyAsync(out, h->d_pred_out, doubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MPPI_OK;
+}
+
+mppi_status mppi_predicted_optimal(mppi_handle *h, double *out)
+{
+    if (!h || !out) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
+    if (!h->published_once) return fail(h, MPPI_ERR_INVALID, "predicted optimal rollout: no update has published yet");
+    HIP_TRY(hipSetDevice(h->device));
+    mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
+    if (st != MPPI_OK) return st;
+    const std::vector<PredictRow> rows{PredictRow{0, h->opt_rec_compact ? 1 : 0, 0}};
+    return predicted_run(h, h->d_rec_opt, rows, h->stream_opt, out);
+}
+
+mppi_status mppi_predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out)
+{
+    if (!h || n < 0 || (n > 0 && (!rollouts || !out))) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
+    if (!h->updated_once) return fail(h, MPPI_ERR_INVALID, "predicted rollouts: no update has run yet");
+    if (h->info[MPPI_INFO_WAIT_TIMEOUTS] != 0)
+        return fail(h, MPPI_ERR_DEVICE, "predicted rollouts: the last update's launch lost rows (in-launch wait timeouts)");
+    std::vector<PredictRow> rows((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t r = rollouts[i];
+        if (r < 0 || r >= h->R)
+            return fail(h, MPPI_ERR_INVALID, "predicted rollouts: index " + std::to_string(r) + " outside [0, " + std::to_string(h->R) + ")");
+        int compact = 0;
+        if (r < h->begin || r >= h->begin + h->count || !predict_row(h->plan, (int)h->H, r - h->begin, &rows[(size_t)i].offset, &compact))
+            return fail(h, MPPI_ERR_INVALID, "predicted rollouts: index " + std::to_string(r) + " outside this shard's [" +
+                                                 std::to_string(h->begin) + ", " + std::to_string(h->begin + h->count) + ")");
+        rows[(size_t)i].compact = compact;
+        rows[(size_t)i].pad = 0;
+    }
+    if (n == 0) return MPPI_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    return predicted_run(h, h->d_rec, rows, h->stream, out);
 }
 
 mppi_status mppi_argmin(mppi_handle *h, int64_t *rollout)

@@ -6,6 +6,8 @@ the output is byte-identical to include/mppi_amd_logging.hpp's logger::MPPI (SUR
 import os
 import sys
 
+from . import abi
+
 _DBL_MIN = sys.float_info.min   # std::numeric_limits<double>::min() (logging/mppi.cpp:81)
 
 
@@ -39,7 +41,7 @@ class MPPILogger:
     """logger::MPPI: `log(trajectory)` once per update (repeated times are skipped)."""
 
     def __init__(self, folder, control_dof, rollouts, log_costs=True, log_weights=True, log_gradient=True,
-                 log_optimal_rollout=True, log_optimal_cost=True, log_update=True):
+                 log_optimal_rollout=True, log_optimal_cost=True, log_update=True, log_predicted=False):
         control = ["control%d" % i for i in range(1, control_dof + 1)]
         rolls = ["rollout%d" % i for i in range(1, rollouts + 1)]
         p = lambda name: os.path.join(folder, name)  # noqa: E731
@@ -49,6 +51,11 @@ class MPPILogger:
         self._optimal_rollout = _CSV(p("optimal_rollout.csv"), ["update", "time"] + control) if log_optimal_rollout else None
         self._optimal_cost = _CSV(p("optimal_cost.csv"), ["update", "time", "cost"]) if log_optimal_cost else None
         self._update = _CSV(p("update.csv"), ["update", "time", "update_duration"]) if log_update else None
+        # beyond the reference (off by default): the optimal rollout's predicted states and positions
+        frames = ["ee", "arm_mount"] + list(abi.LINK_NAMES)
+        predicted = (["q%d" % i for i in range(12)] + ["v%d" % i for i in range(12)] + ["energy"] +
+                     [f + a for f in frames for a in ("_x", "_y", "_z")])
+        self._predicted = _CSV(p("predicted.csv"), ["update", "time"] + predicted) if log_predicted else None
         self._last = _DBL_MIN
 
     def log(self, trajectory):
@@ -74,9 +81,13 @@ class MPPILogger:
                 self._optimal_rollout.write(it, times[i], u[i])
         if self._optimal_cost:
             self._optimal_cost.write(it, time, [trajectory.get_optimal_total_cost()])
+        if self._predicted:
+            rows = trajectory.predicted_optimal().raw
+            for i in range(steps):
+                self._predicted.write(it, times[i], rows[i])
         self._last = time
 
     def close(self):
-        for f in (self._costs, self._weights, self._gradient, self._optimal_rollout, self._optimal_cost, self._update):
+        for f in (self._costs, self._weights, self._gradient, self._optimal_rollout, self._optimal_cost, self._update, self._predicted):
             if f:
                 f.close()

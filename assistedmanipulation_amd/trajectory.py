@@ -175,6 +175,27 @@ def comm_unique_id():
     return buf.raw
 
 
+class Predicted:
+    """Predicted trajectories (mppi_predicted_optimal / mppi_predicted_rollouts): `raw` is the
+    (..., H, MPPI_PRED_N) array, the rest are views of it.  Row k is the state x_k at which step k's
+    cost is evaluated (row 0 the update's state) at `time[k]` = t0 + k dt; the positions are forward
+    kinematics at q_k itself.  `energy` is NaN unless the rollouts integrate the tank; from a
+    rollout's first non-finite state on, its rows are NaN.  `rollouts`: the indices asked for (None
+    for the optimal rollout)."""
+
+    def __init__(self, raw, t0, dt, rollouts=None):
+        H = raw.shape[-2]
+        self.raw = raw
+        self.rollouts = rollouts
+        self.time = t0 + np.arange(H) * dt
+        self.position = raw[..., abi.MPPI_PRED_Q:abi.MPPI_PRED_Q + 12]
+        self.velocity = raw[..., abi.MPPI_PRED_QD:abi.MPPI_PRED_QD + 12]
+        self.energy = raw[..., abi.MPPI_PRED_ENERGY]
+        self.end_effector = raw[..., abi.MPPI_PRED_EE:abi.MPPI_PRED_EE + 3]
+        self.arm_mount = raw[..., abi.MPPI_PRED_ARM_MOUNT:abi.MPPI_PRED_ARM_MOUNT + 3]
+        self.links = raw[..., abi.MPPI_PRED_LINKS:abi.MPPI_PRED_N].reshape(raw.shape[:-1] + (abi.MPPI_LINK_N, 3))
+
+
 class CUpdateEntry(tuple):
     """(fn, handle, state pointer) of Trajectory.c_update_entry, holding the Trajectory alive."""
 
@@ -478,6 +499,29 @@ class Trajectory:
         workspace, energy tank, joint velocity, trajectory, manipulability): the accumulators
         BaseTest / logger::AssistedManipulation read after filter() (mppi_optimal_terms)."""
         return self._vec(self._L.mppi_optimal_terms, 7)
+
+    # -- predicted trajectories -------------------------------------------------------------
+    def predicted_optimal(self):
+        """Where the robot goes under the published plan (mppi_predicted_optimal): a Predicted of H
+        rows, row k the state x_k of the optimal rollout and the positions at q_k."""
+        raw = np.zeros((self.H, abi.MPPI_PRED_N))
+        self._check(self._L.mppi_predicted_optimal(self._h, _p(raw)))
+        return Predicted(raw, self.get_update_last(), self.get_time_step())
+
+    def predicted_rollouts(self, indices):
+        """The same for rollouts of the last update by global index (mppi_predicted_rollouts): a
+        Predicted whose arrays lead with the rollout, in the order of `indices`."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        raw = np.zeros((idx.size, self.H, abi.MPPI_PRED_N))
+        self._check(self._L.mppi_predicted_rollouts(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, _p(raw)))
+        return Predicted(raw, self.get_update_last(), self.get_time_step(), idx)
+
+    def predicted_best(self, n):
+        """predicted_rollouts of the n rollouts with the lowest costs, in cost order: NaN costs last,
+        equal costs by index (the engine's stable order of the costs)."""
+        c = self.costs()
+        order = np.argsort(np.where(np.isnan(c), np.inf, c), kind="stable")
+        return self.predicted_rollouts(order[:max(0, min(int(n), self.R))])
 
     def argmin(self):
         i = C.c_int64()

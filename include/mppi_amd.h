@@ -417,6 +417,40 @@ mppi_status mppi_argmin(mppi_handle *h, int64_t *rollout);
 #define MPPI_TERM_TRAJECTORY 5       /* get_trajectory_cost()       (.hpp:252-254) */
 #define MPPI_TERM_MANIPULABILITY 6   /* get_manipulability_cost()   (.hpp:256-258) */
 mppi_status mppi_optimal_terms(mppi_handle *h, double *terms7);
+
+/* Predicted trajectories: where the robot goes under the published plan (the filter() row
+ * mppi_optimal_terms answers for) and under the rollouts of the last update.  The reference offers
+ * only get_optimal_dynamics(), the last state of thread 0's object (mppi.hpp:456-462); the device
+ * keeps every rollout's step records until the next launch and answers from them.  One row of
+ * MPPI_PRED_N doubles per horizon step:
+ *   row k (k < H) is the state x_k at which step k's cost is evaluated, so row 0 is the update's
+ *   state; x_H is never computed.  The six wrench slots of the state do not change during a rollout
+ *   and are left out.
+ *   The positions are forward kinematics at q_k itself - not the one-step-lagged kinematics the
+ *   objective sees (the end effector at q_{k-1}, as MPPI_LINK_POSITIONS_KINEMATIC's links).
+ *   MPPI_PRED_LINKS: row 0 the universe, row 1 + i body i's frame origin in the world.
+ * NaN rule: from the first step whose q, qd (or E, where the tank is integrated) is not finite, every
+ * column of that row and of all later rows of the rollout is NaN, whatever the launch stored behind
+ * it.  A rollout whose cost is NaN while its states stay finite keeps its finite rows.
+ * FrankaRidgeback handles only (MPPI_ERR_UNSUPPORTED otherwise).  Like mppi_costs, not to be called
+ * concurrently with an update.  These functions came after ABI version 5 without a version change
+ * (no struct changed): detect them by symbol. */
+#define MPPI_PRED_Q 0           /* q_k, 12 */
+#define MPPI_PRED_QD 12         /* qd_k, 12 */
+#define MPPI_PRED_ENERGY 24     /* tank level E_k; NaN unless the handle's launches integrate the tank */
+#define MPPI_PRED_EE 25         /* grasp-frame position at q_k, 3 */
+#define MPPI_PRED_ARM_MOUNT 28  /* arm-mount frame position at q_k, 3 */
+#define MPPI_PRED_LINKS 31      /* world origin of link L (MPPI_LINK_*) at q_k, 13 x 3 */
+#define MPPI_PRED_N 70
+/* The optimal rollout of the last published update (H x MPPI_PRED_N): MPPI_ERR_INVALID before the
+ * first published update; otherwise waits for (or runs) that update's filter() as mppi_optimal_terms
+ * does. */
+mppi_status mppi_predicted_optimal(mppi_handle *h, double *out_HxN);
+/* n rollouts of the last rollout launch by global rollout index (n x H x MPPI_PRED_N, in the order
+ * asked for; n = 0 is a no-op).  MPPI_ERR_INVALID before the first update, for an index outside
+ * [0, R) and, on a sharded handle, outside its own [begin, begin + count); MPPI_ERR_DEVICE after an
+ * update that failed with in-launch wait timeouts (rows were lost). */
+mppi_status mppi_predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out_nxHxN);
 mppi_status mppi_update_duration(mppi_handle *h, double *seconds);
 /* Trajectory::get_update_last (mppi.hpp:381-384): the time of the last successful update, whichever
  * entry made it (mppi_update, the phase-split calls); the count is MPPI_INFO_UPDATE_COUNT. */

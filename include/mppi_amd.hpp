@@ -311,6 +311,18 @@ public:
     }
     const Dynamics &get_optimal_dynamics() const { return *m_dynamics; }
 
+    // Where the robot goes under the published plan and under the last update's rollouts
+    // (mppi_predicted_optimal / mppi_predicted_rollouts): rows of MPPI_PRED_N doubles, row k the
+    // state x_k (MPPI_PRED_Q, _QD, _ENERGY) and the frame and link positions at q_k (MPPI_PRED_EE,
+    // _ARM_MOUNT, _LINKS); H rows, and n x H rows in the order of `rollouts` (global indices).
+    std::vector<double> get_predicted_optimal() const { return fetch(mppi_predicted_optimal, (size_t)(m_H * MPPI_PRED_N)); }
+    std::vector<double> get_predicted_rollouts(const std::vector<int64_t> &rollouts) const
+    {
+        std::vector<double> v(rollouts.size() * (size_t)(m_H * MPPI_PRED_N));
+        check(mppi_predicted_rollouts(m_h, rollouts.data(), (int64_t)rollouts.size(), v.data()));
+        return v;
+    }
+
     // Per-update inputs and parity hooks of the device engine.
     template <class Vec>
     void set_forecast(const Vec &wrench_Hx6) { check(mppi_set_forecast(m_h, wrench_Hx6.data())); }

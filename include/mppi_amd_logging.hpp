@@ -9,6 +9,11 @@
 //   optimal_rollout.csv                                             time = t + k dt
 //   optimal_cost.csv              update, time, cost
 //   update.csv                    update, time, update_duration
+//
+// Beyond the reference (off by default, so the files above are all a default logger writes):
+//   predicted.csv                 update, time, q0..q11, v0..v11, energy, ee_x/y/z,
+//                                 arm_mount_x/y/z, <link name>_x/y/z   one row per horizon step of
+//                                 the optimal rollout (mppi_predicted_optimal), time = t + k dt
 #pragma once
 
 #include <cstddef>
@@ -100,6 +105,7 @@ public:
         bool log_optimal_rollout = true;
         bool log_optimal_cost = true;
         bool log_update = true;
+        bool log_predicted = false;   // predicted.csv: the optimal rollout's predicted states and positions
     };
 
     static std::unique_ptr<MPPI> create(const Configuration &configuration)
@@ -120,7 +126,18 @@ public:
         if (configuration.log_optimal_rollout) mppi->m_optimal_rollout = CSV::create({f / "optimal_rollout.csv", header(control)});
         if (configuration.log_optimal_cost) mppi->m_optimal_cost = CSV::create({f / "optimal_cost.csv", header({"cost"})});
         if (configuration.log_update) mppi->m_update = CSV::create({f / "update.csv", header({"update_duration"})});
-        const bool error = (configuration.log_costs && !mppi->m_costs) || (configuration.log_weights && !mppi->m_weights) ||
+        if (configuration.log_predicted) {
+            CSV::Header row;
+            for (int i = 0; i < MPPI_FR_JOINTS; i++) row.push_back("q" + std::to_string(i));
+            for (int i = 0; i < MPPI_FR_JOINTS; i++) row.push_back("v" + std::to_string(i));
+            row.push_back("energy");
+            std::vector<std::string> frames{"ee", "arm_mount"};
+            for (int l = 0; l < MPPI_LINK_N; l++) frames.push_back(mppi_link_name(l));
+            for (const std::string &name : frames)
+                for (const char *axis : {"_x", "_y", "_z"}) row.push_back(name + axis);
+            mppi->m_predicted = CSV::create({f / "predicted.csv", header(row)});
+        }
+        const bool error = (configuration.log_predicted && !mppi->m_predicted) || (configuration.log_costs && !mppi->m_costs) || (configuration.log_weights && !mppi->m_weights) ||
                            (configuration.log_gradient && !mppi->m_gradient) ||
                            (configuration.log_optimal_rollout && !mppi->m_optimal_rollout) ||
                            (configuration.log_optimal_cost && !mppi->m_optimal_cost) || (configuration.log_update && !mppi->m_update);
@@ -161,12 +178,17 @@ public:
             for (unsigned int i = 0; i < steps; ++i) m_optimal_rollout->write(iteration, m_time[i], u.data() + (std::size_t)i * C, C);
         }
         if (m_optimal_cost) m_optimal_cost->write(iteration, time, trajectory.get_optimal_total_cost());
+        if (m_predicted) {
+            const std::vector<double> p = trajectory.get_predicted_optimal();
+            for (unsigned int i = 0; i < steps; ++i)
+                m_predicted->write(iteration, m_time[i], p.data() + (std::size_t)i * MPPI_PRED_N, MPPI_PRED_N);
+        }
         m_last_update = time;
     }
 
 private:
     MPPI() = default;
-    std::unique_ptr<CSV> m_costs, m_weights, m_gradient, m_optimal_rollout, m_optimal_cost, m_update;
+    std::unique_ptr<CSV> m_costs, m_weights, m_gradient, m_optimal_rollout, m_optimal_cost, m_update, m_predicted;
     std::vector<double> m_time;
     double m_last_update = 0.0;
 };
