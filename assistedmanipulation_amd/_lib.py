@@ -92,6 +92,12 @@ PROTOTYPES = {
     "mppi_get_link_positions": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "mppi_dynamics_set_link_positions": (C.c_int, [_h, C.c_int]),
     "mppi_dynamics_link_positions": (C.c_int, [_h, _dp]),
+    "mppi_set_simulated_wrench": (C.c_int, [_h, C.c_int]),
+    "mppi_get_simulated_wrench": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_dynamics_add_end_effector_simulated_wrench": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_get_end_effector_simulated_wrench": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_set_simulated_wrench": (C.c_int, [_h, C.c_int]),
+    "mppi_dynamics_get_simulated_wrench": (C.c_int, [_h, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -59,6 +59,11 @@ LINK_NAMES = ("omni_base_root_link", "x_slider", "y_slider", "pivot", "panda_lin
               "panda_link4", "panda_link5", "panda_link6", "panda_link7", "panda_leftfinger", "panda_rightfinger")
 MPPI_LINK_POSITIONS_ZERO = 0
 MPPI_LINK_POSITIONS_KINEMATIC = 1
+# mppi_set_simulated_wrench / mppi_dynamics_set_simulated_wrench
+MPPI_SIMULATED_WRENCH_OFF = 0
+MPPI_SIMULATED_WRENCH_STATE = 1
+MPPI_SIMULATED_WRENCH_FORECAST = 2
+MPPI_SIMULATED_WRENCH_ON = 1
 # One row of mppi_predicted_optimal / mppi_predicted_rollouts (MPPI_PRED_*): q_k, qd_k, the tank level,
 # then the grasp-frame, arm-mount and link positions at q_k
 MPPI_PRED_Q, MPPI_PRED_QD, MPPI_PRED_ENERGY, MPPI_PRED_EE, MPPI_PRED_ARM_MOUNT, MPPI_PRED_LINKS = 0, 12, 24, 25, 28, 31

@@ -83,6 +83,22 @@ bool env_link_positions(int &mode, std::string &why)
     return false;
 }
 
+// MPPI_SIMULATED_WRENCH: the simulated-wrench mode new handles start in (0 off, 1 the state's
+// wrench, 2 the forecast's rows; new dynamics objects: 0 off, 1 or 2 on).  Unset: off.  The whole
+// string must be "0", "1" or "2"; false with a message otherwise.
+bool env_simulated_wrench(int &mode, std::string &why)
+{
+    mode = MPPI_SIMULATED_WRENCH_OFF;
+    const char *e = std::getenv("MPPI_SIMULATED_WRENCH");
+    if (!e) return true;
+    if (e[0] >= '0' && e[0] <= '2' && e[1] == '\0') {
+        mode = e[0] - '0';
+        return true;
+    }
+    why = std::string("MPPI_SIMULATED_WRENCH must be 0, 1 or 2, not \"") + e + "\"";
+    return false;
+}
+
 struct DeviceBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -134,6 +150,13 @@ struct mppi_handle {
     // mppi_set_link_positions: MPPI_LINK_POSITIONS_ZERO (the reference's stub) or _KINEMATIC; fixed
     // once the first update has run (the launch plan and a captured graph hold its kernels)
     int link_positions = MPPI_LINK_POSITIONS_ZERO;
+    // mppi_set_simulated_wrench: MPPI_SIMULATED_WRENCH_OFF (the reference's stub), _STATE or
+    // _FORECAST; fixed once the first update has run, like link_positions.  Each update writes its
+    // wrench rows behind its step constants (d_steps + H, launch_wrench_table); the hipGraph path
+    // launches that ahead of the graph (wrench_ahead: phase 1 then leaves it out).
+    int simulated_wrench = MPPI_SIMULATED_WRENCH_OFF;
+    bool wrench_ahead = false;
+    double *d_fc_rows = nullptr;    // [H][6] the caller's forecast table on the device (upload_steps)
     int64_t S = 0, K = 0, R = 0, H = 0, C = 0, X = 0;
     double dt = 0, gradient_step = 0, cost_scale = 0, gamma = 1;
     int control_bound = 0;
@@ -183,7 +206,9 @@ struct mppi_handle {
     double *d_gamma = nullptr;      // [H] pow(gamma, k) (host std::pow)
     double *d_fc_out = nullptr;     // [6] forecast_eval result
     double *d_terms = nullptr;      // [7] mppi_optimal_terms
-    StepConst *d_steps_buf[2] = {nullptr, nullptr};   // per-update constants, alternate updates
+    // per-update constants, alternate updates: H StepConst, then the H simulated-wrench rows
+    // (kernels.hpp FR_WRENCH_ROW) of the same update
+    StepConst *d_steps_buf[2] = {nullptr, nullptr};
     mppi_assisted_manipulation_desc am{};
     mppi_quadratic_cost_desc quad{};
     double pm_mass = 1.0;
@@ -439,6 +464,9 @@ mppi_status upload_steps(mppi_handle *h)
     build_steps(h, steps);
     for (StepConst *d : h->d_steps_buf)
         HIP_TRY(hipMemcpyAsync(d, steps.data(), steps.size() * sizeof(StepConst), hipMemcpyHostToDevice, h->stream));
+    // the table's rows for the simulated wrench's FORECAST mode (zeros without a table)
+    if (h->forecast.empty()) HIP_TRY(hipMemsetAsync(h->d_fc_rows, 0, (size_t)(6 * h->H) * sizeof(double), h->stream));
+    else HIP_TRY(hipMemcpyAsync(h->d_fc_rows, h->forecast.data(), (size_t)(6 * h->H) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MPPI_OK;
 }
@@ -627,6 +655,11 @@ struct mppi_dynamics {
     size_t buf_doubles = 0;
     DevPinocchio *h_obj = nullptr;   // pinned host copy for the queries
     int link_positions = MPPI_LINK_POSITIONS_ZERO;   // mppi_dynamics_set_link_positions
+    // add_end_effector_simulated_wrench's running sum (the next step applies and zeroes it), the
+    // wrench the last step applied, and whether forecast() adds its rows (mppi_dynamics_set_simulated_wrench)
+    double wrench_sum[6] = {0, 0, 0, 0, 0, 0}, wrench_applied[6] = {0, 0, 0, 0, 0, 0};
+    bool wrench_pending = false;
+    int simulated_wrench = MPPI_SIMULATED_WRENCH_OFF;
     std::string err;
 };
 
@@ -711,9 +744,12 @@ mppi_status mppi_dynamics_create(const mppi_dynamics_desc *desc, const double *i
     if (check_topology(desc->frankaridgeback, why) != MPPI_OK) return dfail(nullptr, MPPI_ERR_UNSUPPORTED, why);
     int link_mode = 0;
     if (!env_link_positions(link_mode, why)) return dfail(nullptr, MPPI_ERR_INVALID, why);
+    int wrench_mode = 0;
+    if (!env_simulated_wrench(wrench_mode, why)) return dfail(nullptr, MPPI_ERR_INVALID, why);
     d = new mppi_dynamics();
     d->device = device;
     d->link_positions = link_mode;
+    d->simulated_wrench = wrench_mode != MPPI_SIMULATED_WRENCH_OFF ? MPPI_SIMULATED_WRENCH_ON : MPPI_SIMULATED_WRENCH_OFF;
     auto bail = [&](mppi_status st) {
         std::string m = d->err;
         mppi_dynamics_destroy(d);
@@ -772,8 +808,15 @@ mppi_status mppi_dynamics_step(mppi_dynamics *d, const double *control, double d
     a.op = OBJ_STEP;
     std::memcpy(a.u, control, FR_C * sizeof(double));
     a.dt = dt;
+    // the wrench added since the last step: applied now, then zeroed.  With nothing added the step
+    // runs without the term (bit for bit the step of an object that never saw a wrench).
+    a.has_wrench = d->wrench_pending ? 1 : 0;
+    std::memcpy(a.w, d->wrench_sum, sizeof(a.w));
     mppi_status st = obj_run(d, a);
     if (st != MPPI_OK) return st;
+    std::memcpy(d->wrench_applied, d->wrench_sum, sizeof(d->wrench_applied));
+    for (double &v : d->wrench_sum) v = 0.0;
+    d->wrench_pending = false;
     if (!state_out) {
         DHIP_TRY(hipStreamSynchronize(d->stream));
         return MPPI_OK;
@@ -838,8 +881,17 @@ mppi_status mppi_dynamics_forecast(mppi_dynamics *d, const double *state, double
         DHIP_TRY(hipMemcpyAsync(d->d_buf + rows, wrench, wrows * sizeof(double), hipMemcpyHostToDevice, d->stream));
         a.wrench = d->d_buf + rows;
     }
+    // ON: row k joins the simulated wrench before step k (dynamics.cpp:127); what the caller added
+    // before the call goes into the first step either way
+    a.wrench_rows = (d->simulated_wrench == MPPI_SIMULATED_WRENCH_ON && wrench) ? 1 : 0;
+    a.has_wrench = d->wrench_pending ? 1 : 0;
+    std::memcpy(a.w, d->wrench_sum, sizeof(a.w));
     st = obj_run(d, a);
     if (st != MPPI_OK) return st;
+    for (int i = 0; i < 6; i++)   // the wrench the last of the steps applied
+        d->wrench_applied[i] = (steps == 1 ? d->wrench_sum[i] : 0.0) + (a.wrench_rows ? wrench[(steps - 1) * 6 + i] : 0.0);
+    for (double &v : d->wrench_sum) v = 0.0;
+    d->wrench_pending = false;
     DHIP_TRY(hipMemcpyAsync(out, d->d_buf, rows * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     DHIP_TRY(hipStreamSynchronize(d->stream));
     return MPPI_OK;
@@ -889,6 +941,37 @@ mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out)
     if (st != MPPI_OK) return st;
     static_assert(MPPI_LINK_N == FR_LINKS, "Link enum");
     std::memcpy(out, d->h_obj->link, 3 * MPPI_LINK_N * sizeof(double));
+    return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_add_end_effector_simulated_wrench(mppi_dynamics *d, const double *wrench6)
+{
+    if (!d || !wrench6) return MPPI_ERR_INVALID;
+    for (int i = 0; i < 6; i++) d->wrench_sum[i] += wrench6[i];
+    d->wrench_pending = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_get_end_effector_simulated_wrench(mppi_dynamics *d, double *out6)
+{
+    if (!d || !out6) return MPPI_ERR_INVALID;
+    std::memcpy(out6, d->wrench_applied, 6 * sizeof(double));
+    return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_set_simulated_wrench(mppi_dynamics *d, int mode)
+{
+    if (!d) return MPPI_ERR_INVALID;
+    if (mode != MPPI_SIMULATED_WRENCH_OFF && mode != MPPI_SIMULATED_WRENCH_ON)
+        return dfail(d, MPPI_ERR_INVALID, "simulated wrench of a dynamics object must be MPPI_SIMULATED_WRENCH_OFF or MPPI_SIMULATED_WRENCH_ON");
+    d->simulated_wrench = mode;
+    return MPPI_OK;
+}
+
+mppi_status mppi_dynamics_get_simulated_wrench(mppi_dynamics *d, int *mode)
+{
+    if (!d || !mode) return MPPI_ERR_INVALID;
+    *mode = d->simulated_wrench;
     return MPPI_OK;
 }
 
@@ -966,9 +1049,12 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
 
     int link_mode = 0;
     if (!env_link_positions(link_mode, why)) return fail(nullptr, MPPI_ERR_INVALID, why);
+    int wrench_mode = 0;
+    if (!env_simulated_wrench(wrench_mode, why)) return fail(nullptr, MPPI_ERR_INVALID, why);
     h = new mppi_handle();
     h->env = env;
     if (dyn->kind == MPPI_DYNAMICS_FRANKARIDGEBACK) h->link_positions = link_mode;
+    if (dyn->kind == MPPI_DYNAMICS_FRANKARIDGEBACK) h->simulated_wrench = wrench_mode;
     {
         const char *e = getenv("MPPI_HOST_TRACE");
         h->host_trace = e && e[0] == '1';
@@ -1072,8 +1158,9 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
     CREATE_TRY(dalloc(h, &h->d_rank, (size_t)h->R));
     CREATE_TRY(dalloc(h, &h->d_rank_keys, (size_t)rank_scratch(h->S)));
     CREATE_TRY(dalloc(h, &h->d_status, 1));
-    CREATE_TRY(dalloc(h, &h->d_steps_buf[0], (size_t)h->H));
-    CREATE_TRY(dalloc(h, &h->d_steps_buf[1], (size_t)h->H));
+    CREATE_TRY(dalloc(h, &h->d_steps_buf[0], (size_t)(2 * h->H)));   // (the second half: the wrench rows, zeros)
+    CREATE_TRY(dalloc(h, &h->d_steps_buf[1], (size_t)(2 * h->H)));
+    CREATE_TRY(dalloc(h, &h->d_fc_rows, (size_t)(6 * h->H)));
     h->d_steps = h->d_steps_buf[0];
     CREATE_TRY(dalloc(h, &h->d_gamma, (size_t)h->H));
     CREATE_TRY(dalloc(h, &h->d_fc_out, 6));
@@ -1607,6 +1694,7 @@ static mppi_status launch_filter_standalone(mppi_handle *h)
         a.energy = h->cost_kind == MPPI_COST_ASSISTED_MANIPULATION && h->am.enable_energy_limit;
         a.rec = h->d_rec_opt;
         a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
+        a.simulated_wrench = h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF;   // (its update's rows: opt_steps + H)
         // the row's objective after its loop (fr_coop_kernel's one-wave path)
         a.costs_in_launch = fr_coop_costs_in_launch(h->env) ? 1 : 0;
         HIP_TRY(launch_fr_coop(a, h->stream_opt));
@@ -1638,6 +1726,33 @@ static mppi_status launch_filter_standalone(mppi_handle *h)
 static WGradArgs wgrad_args(const mppi_handle *h);
 static FinishArgs finish_args(mppi_handle *h);
 
+// The simulated wrench's rows of this update, behind its step constants.  The state's wrench changes
+// with every update, so the buffers alternate as they do with an attached forecast: the pending
+// filter() of the previous update reads the other one (with a caller's table both hold the same
+// step constants, upload_steps).  Written like the step constants: one small launch on the engine
+// stream ahead of the rollouts, its inputs by value.
+static mppi_status write_wrench_rows(mppi_handle *h, const double *state, double time)
+{
+    h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
+    WrenchTableArgs w{};
+    w.f = forecast_args(h);
+    w.H = (int)h->H;
+    w.t0 = time;
+    w.dt = h->dt;
+    w.out = reinterpret_cast<double *>(h->d_steps + h->H);
+    if (h->simulated_wrench == MPPI_SIMULATED_WRENCH_STATE) {
+        w.source = WT_CONST;   // x[24..30): the end-effector wrench slots of the state (what line 240 read)
+        for (int i = 0; i < 6; i++) w.w[i] = state[2 * FR_NB + i];
+    } else if (h->fc.type != FC_NONE) {
+        w.source = WT_FORECAST;
+    } else {
+        w.source = WT_TABLE;
+        w.table = h->d_fc_rows;
+    }
+    HIP_TRY(launch_wrench_table(w, h->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
 {
     if (!h || !state) return MPPI_ERR_INVALID;
@@ -1653,6 +1768,10 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
     if (h->fc.type != FC_NONE) {   // this update's forecast samples, t0 + k dt (mppi.cpp:326)
         h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];   // the previous filter() reads the other
         HIP_TRY(launch_forecast_steps(forecast_args(h), step_params(h), h->d_gamma, (int)h->H, time, h->dt, h->d_steps, h->stream));
+    }
+    if (h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF && !h->wrench_ahead) {
+        mppi_status st = write_wrench_rows(h, state, time);
+        if (st != MPPI_OK) return st;
     }
 
     // sample(): shift count by truncation (mppi.cpp:194-201)
@@ -1752,6 +1871,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         a.rtoken = ++h->relay_token ? h->relay_token : ++h->relay_token;   // (never 0)
         a.stage_work = h->env.stage_work_off ? 0 : 1;
         a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
+        a.simulated_wrench = h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF;
         // sharded: this rank's wait timeouts into cost slot R, which the all-reduce carries to every rank
         a.wait_sum = h->comm ? h->d_costs_local + h->R : (sharded(h) ? h->d_costs + h->R : nullptr);
         if (h->debug_updates > 0) {   // mppi_debug_inject: this update's launch carries the fault
@@ -2203,9 +2323,18 @@ static mppi_status update_graph(mppi_handle *h, const double *state, double time
     const bool capture = h->graph_exec == nullptr;
     const bool coll = h->comm != nullptr;
     const UpdateSnapshot snap = snapshot_update(h);
+    // the simulated wrench's rows: a launch ahead of the graph, on the same stream (its arguments
+    // change with every update and it is not one of the graph's nodes); the rollout nodes take the
+    // rows' buffer with their step constants
+    if (h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF) {
+        mppi_status ws = write_wrench_rows(h, state, time);
+        if (ws != MPPI_OK) return ws;
+    }
     if (capture) HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     else h->graph_dry = true;
+    h->wrench_ahead = true;
     mppi_status st = mppi_update_phase1(h, state, time);
+    h->wrench_ahead = false;
     if (st == MPPI_OK && coll && capture) st = allreduce_costs(h);
     if (st == MPPI_OK) st = mppi_update_phase2(h);
     if (st == MPPI_OK && coll && capture) st = allreduce_gradient(h);
@@ -2317,6 +2446,28 @@ mppi_status mppi_get_link_positions(mppi_handle *h, int *mode)
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "link positions: FrankaRidgeback handles only");
     *mode = h->link_positions;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_simulated_wrench(mppi_handle *h, int mode)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "simulated wrench: FrankaRidgeback handles only");
+    if (mode != MPPI_SIMULATED_WRENCH_OFF && mode != MPPI_SIMULATED_WRENCH_STATE && mode != MPPI_SIMULATED_WRENCH_FORECAST)
+        return fail(h, MPPI_ERR_INVALID, "simulated wrench must be MPPI_SIMULATED_WRENCH_OFF, _STATE or _FORECAST");
+    // the rollout launches' kernels are part of the launch plan and of a captured graph
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "the simulated wrench is set before the first update");
+    h->simulated_wrench = mode;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode)
+{
+    if (!h || !mode) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "simulated wrench: FrankaRidgeback handles only");
+    *mode = h->simulated_wrench;
     return MPPI_OK;
 }
 

@@ -103,6 +103,29 @@ __global__ __launch_bounds__(64) void forecast_table_kernel(ForecastArgs f, doub
     forecast_eval(f, tk, out + k * 6);
 }
 
+// The rollouts' simulated end-effector wrench of step k (mppi_set_simulated_wrench): the update's
+// state's wrench in every row, row k of the caller's table, or forecast(t0 + k dt) - the time the
+// step constants sample (forecast_steps_kernel).  Rows of FR_WRENCH_ROW doubles, the last two zero.
+__global__ __launch_bounds__(64) void wrench_table_kernel(WrenchTableArgs a)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= a.H) return;
+    double w[6];
+    if (a.source == WT_FORECAST) {
+        double tk;
+        {
+#pragma clang fp contract(off)
+            tk = a.t0 + (double)k * a.dt;
+        }
+        forecast_eval(a.f, tk, w);
+    } else {
+        for (int i = 0; i < 6; i++) w[i] = a.source == WT_TABLE ? a.table[k * 6 + i] : a.w[i];
+    }
+    double *o = a.out + (int64_t)k * FR_WRENCH_ROW;
+    for (int i = 0; i < 6; i++) o[i] = w[i];
+    for (int i = 6; i < FR_WRENCH_ROW; i++) o[i] = 0.0;
+}
+
 __global__ void forecast_eval_kernel(ForecastArgs f, double time, double *out)
 {
     if (threadIdx.x == 0) forecast_eval(f, time, out);
@@ -268,6 +291,13 @@ hipError_t launch_forecast_table(const ForecastArgs &f, double t0, double dt, in
 {
     if (steps <= 0) return hipSuccess;
     hipLaunchKernelGGL(forecast_table_kernel, dim3((unsigned)((steps + 63) / 64)), dim3(64), 0, s, f, t0, dt, steps, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_wrench_table(const WrenchTableArgs &a, hipStream_t s)
+{
+    if (a.H <= 0) return hipSuccess;
+    hipLaunchKernelGGL(wrench_table_kernel, dim3((unsigned)((a.H + 63) / 64)), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

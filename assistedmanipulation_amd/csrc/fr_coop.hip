@@ -58,6 +58,14 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
+// This text is compiled as four translation units: by itself (the default mode's kernels
+// and everything the host calls), and included by fr_coop_lp.hip (FR_COOP_LP_UNIT: the kinematic
+// link-position objective), fr_coop_wr.hip (FR_COOP_WR_UNIT: the simulated end-effector wrench in
+// the step) and fr_coop_wr_lp.hip (both).  A variant unit holds its kernels and their launchers only.
+#if defined(FR_COOP_LP_UNIT) || defined(FR_COOP_WR_UNIT)
+#define FR_COOP_VARIANT_UNIT 1
+#endif
+
 #ifdef PHASE_MARKS
 #define PMARK(n) asm volatile("; PHASE " #n)
 #define PMARK_D(n, x) asm volatile("; PHASE " #n : "+v"(x))
@@ -1016,8 +1024,14 @@ __device__ __forceinline__ double coop_aba(int j, const double *Lk, double *Lw, 
 __device__ __forceinline__ void composite_scan(double *v, const double *m)
 {
     // (no leading s_nop: tools/dpp_hazard_check.py checks every build that the lanes' own (h, Ib),
-    // the DPP sources, were not written in the two instructions before the block)
-    asm(""
+    // the DPP sources, were not written in the two instructions before the block; the simulated
+    // wrench's units, where the compiler places the products h = m c right ahead of it, lead with one)
+#ifdef FR_COOP_WR_UNIT
+#define COMPOSITE_SCAN_LEAD "s_nop 1\n\t"
+#else
+#define COMPOSITE_SCAN_LEAD ""
+#endif
+    asm(COMPOSITE_SCAN_LEAD
         "v_fmac_f64_dpp %0, %0, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %1, %1, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
         "v_fmac_f64_dpp %2, %2, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
@@ -1200,7 +1214,7 @@ __device__ __forceinline__ double coop_solve(int j, const LaneConst &L, const Co
 // Jacobi rotations to its eigenvalues / vectors, l the least eigenvalue, a and b the other two
 // eigenvectors times sqrt(lambda - l) (inertias are positive semi-definite, so l >= 0 and the two
 // excesses are >= 0; rounding is clamped).
-#ifndef FR_COOP_LP_UNIT   // (the table kernel lives in the main unit alone)
+#ifndef FR_COOP_VARIANT_UNIT   // (the table kernel lives in the main unit alone)
 __device__ void inertia_rank2(const double *Ic, double *a, double *b, double *l)
 {
     double A[3][3] = {{Ic[0], Ic[1], Ic[3]}, {Ic[1], Ic[2], Ic[4]}, {Ic[3], Ic[4], Ic[5]}};
@@ -1294,7 +1308,7 @@ __global__ void fr_body_table_kernel(const DevModel *model, const DevCost *cost,
         table[t] = v;
     }
 }
-#endif   // FR_COOP_LP_UNIT
+#endif   // FR_COOP_VARIANT_UNIT
 
 // Stage the body table in LDS.
 __device__ __forceinline__ void stage_body_table(const FrRolloutArgs &a, double *Lmodel, int nt)
@@ -1374,7 +1388,14 @@ constexpr int WAIT_SPINS_ROWS = 1 << 22;
 
 // KC: compact records (FR_REC_C, store_ks: the kinematic sums on the row's chain), else the 768-B
 // ones (store_kin).
-template <int CK, bool EN, bool FROW, int HO = 0, bool PROG = false, bool KC = false>
+// WR: the simulated end-effector wrench (mppi_set_simulated_wrench): step k adds tau_w = J_G(q_k)^T w_k
+// to the torque, w_k = (f, m) row k of the [H][8] table behind the row's step constants (the folded
+// filter() row: behind its own update's), a force and a moment at the grasp frame's origin in world
+// axes.  With the lane's world motion subspace S_j = (v_j; omega_j) and this step's grasp-frame
+// position p_ee (lane 9's kin.fp): tau_w,j = v_j . f + omega_j . (m + p_ee x f) on lanes 0..9, 0 on
+// the fingers'.  Row k + 1 is loaded as soon as step k has used row k (before the step's solve):
+// most of a step ahead, so the load is off the step's chain.  WR = false compiles none of it.
+template <int CK, bool EN, bool FROW, int HO = 0, bool PROG = false, bool KC = false, bool WR = false>
 __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int lane, int wblk, double *Lk, double *Lw,
                                          const double *Lmodel, const double *Lx0, double *Lst = nullptr, int kb = 0,
                                          int ke = 0x7FFFFFFF, int *Lprog = nullptr, int *Lgo = nullptr, int go_val = 0,
@@ -1490,6 +1511,17 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
     // (issued before the first record store: the loop header then waits for the loads alone,
     // vmcnt(2), on the entry edge as on the back edge, not for the stores behind them)
     double eps_n = np[(int64_t)kb * nstride], ub_n = Up[min(kb + ush, H - 1) * FR_C + jb];
+    // WR: the wrench rows [H][FR_WRENCH_ROW] behind the H step constants; row kb now, row k + 1 in
+    // step k (k + 1 <= H - 1: inside the table)
+    const double *wp = nullptr;
+    double w_n[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wmask = 0.0;
+    if constexpr (WR) {
+        wp = reinterpret_cast<const double *>((FROW && frow ? a.fsteps : a.steps) + H);
+#pragma unroll
+        for (int i = 0; i < 6; i++) w_n[i] = wp[(int64_t)min(kb, H - 1) * FR_WRENCH_ROW + i];
+        wmask = j <= FR_EE_PARENT ? 1.0 : 0.0;   // the grasp frame's chain: bodies 0..9
+        asm volatile("" : "+v"(wmask));           // kept in a register across the loop
+    }
     // a relay stage past the first: its setup above and its first loads are in flight while it waits
     // for the previous stage's state (Lgo: the stage counter it raises once Lst is written)
     if constexpr (HO == 3) {
@@ -1604,21 +1636,38 @@ __device__ __forceinline__ int coop_rows(const FrRolloutArgs &a, int64_t lr, int
         // PinocchioDynamics::step: base velocity overwrite, tau = arm controls, calculate, Euler
         const double u = __builtin_fma(eps_l, sd, ub_l * jd);
         qd = base_velocity(L, u, sq, cq, qd);
-        if constexpr (EN)
+        if constexpr (EN && !WR)
             Lw[L_TAU + j] = (j >= 3 && j < 10) ? u : 0.0;   // coop_aba's tau
         coop_fk<CK, EN>(L, q, sq, cq, qd, Mk, Lk, kin, bd, grav);
+        double tau_w = 0.0;
+        if constexpr (WR) {   // J_G(q_k)^T w_k at this calculate()'s configuration
+            const double pe[3] = {bcast<FR_EE_PARENT>(kin.fp[0]), bcast<FR_EE_PARENT>(kin.fp[1]), bcast<FR_EE_PARENT>(kin.fp[2])};
+            double mo[3];   // the moment about the world origin, m + p_ee x f
+            cross3(pe, w_n, mo);
+#pragma unroll
+            for (int i = 0; i < 3; i++) mo[i] = w_n[3 + i] + mo[i];
+            tau_w = wmask * (((bd.S[0] * w_n[0] + bd.S[1] * w_n[1]) + bd.S[2] * w_n[2]) +
+                             ((bd.S[3] * mo[0] + bd.S[4] * mo[1]) + bd.S[5] * mo[2]));
+            // row k + 1 into the same registers, most of a step ahead of its use and ahead of this
+            // step's record stores (no second set of six doubles across the solve)
+#pragma unroll
+            for (int i = 0; i < 6; i++) w_n[i] = wp[(int64_t)(k + 1) * FR_WRENCH_ROW + i];
+            if constexpr (EN) Lw[L_TAU + j] = ((j >= 3 && j < 10) ? u : 0.0) + tau_w;   // coop_aba's tau
+        }
         // the next record's kinematics (the one-step lag)
         if constexpr (KC) store_ks<CK, EN>(recp(k + 1), j, L, bd, qd, Lk);
         else store_kin<CK>(recp(k + 1), j, bd, qd);
         double pe = 0.0;
         double qdd;
         if constexpr (EN) qdd = coop_aba<EN>(j, Lk, Lw, pe);
+        else if constexpr (WR) qdd = coop_solve(j, L, bd, u * L.taud + tau_w, Lk);
         else qdd = coop_solve(j, L, bd, u * L.taud, Lk);
         PMARK_D(7, qdd);
         qd = qd + qdd * a.dt;
         q = q + qd * a.dt;
         if constexpr (EN) {   // power = (tau_u + NLE) . v_new; EnergyTank::step (energy.hpp:19-22)
-            const double tau_l = (j >= 3 && j < 10) ? u : 0.0;
+            double tau_l = (j >= 3 && j < 10) ? u : 0.0;
+            if constexpr (WR) tau_l = tau_l + tau_w;   // m_joint_torque holds the wrench's torque too
             const double power = bsum<0, FR_NB>(tau_l * qd + kin.pw, 1.0) + a.dt * bsum<0, 6>(pe, 1.0);
             E = smax(0.0, E + power * a.dt);
         }
@@ -2090,7 +2139,7 @@ __device__ __forceinline__ int relay_step(const FrRolloutArgs &a, int r, int H)
 // hand-off crosses workgroups, once per member.  Without a.handover wave 4 runs every step itself
 // at the main waves' priority (the doubled SIMD of round 2, kept for A/B).  Returns whether the
 // stage ran (false: the previous stage never signalled, counted in Status::wait_timeouts).
-template <int CK, bool EN>
+template <int CK, bool EN, bool WR = false>
 __device__ __forceinline__ bool relay_stage(const FrRolloutArgs &a, int s, int m, int lane, double *Lk, double *Lw,
                                             const double *Lmodel, const double *Lx0, int *Lflag, int *Lq, double *Lst,
                                             bool drawn = false)
@@ -2118,7 +2167,7 @@ __device__ __forceinline__ bool relay_stage(const FrRolloutArgs &a, int s, int m
     // one call site: one copy of the step loop for both shapes.  A stage past a member's first makes
     // its setup and first loads, then waits inside for the previous stage's state (Lq[Q_STAGE] == s;
     // bounded, about 0.2 s: -2 if it gave up)
-    if (coop_rows<CK, EN, true, 3>(a, xlr, lane, wblk, Lk, Lw, Lmodel, Lx0, Lst, kb, ke, nullptr,
+    if (coop_rows<CK, EN, true, 3, false, false, WR>(a, xlr, lane, wblk, Lk, Lw, Lmodel, Lx0, Lst, kb, ke, nullptr,
                                    (a.handover && s > 0) ? Lq + Q_STAGE : nullptr, s,
                                    (a.handover && s == 0 && m > 0) ? a.rx + q : nullptr, m) == -2)
         return false;
@@ -2240,21 +2289,35 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // of their own (fr_coop_lp.hip, which includes this file with FR_COOP_LP_UNIT): in one unit with the
 // default mode's kernels they changed fr_coop_x_kernel's scalar code, and apart the default mode's
 // are the same functions, by name and by instruction.
-#ifndef FR_COOP_LP_UNIT
-template <int CK, bool EN, int WPB, bool KC>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_kernel(FrRolloutArgs a)
-{
-    constexpr bool LP = false;
-#include "fr_coop_kernel_body.inc"
-}
+// WR: the simulated end-effector wrench in the step (FrRolloutArgs::simulated_wrench, coop_rows),
+// again kernels and units of their own (fr_coop_wr.hip; with LP, fr_coop_wr_lp.hip).
+#if defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
+#define FR_COOP_K fr_coop_wr_lp_kernel
+#define FR_COOP_XK fr_coop_x_wr_lp_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR true
+#elif defined(FR_COOP_WR_UNIT)
+#define FR_COOP_K fr_coop_wr_kernel
+#define FR_COOP_XK fr_coop_x_wr_kernel
+#define FR_UNIT_LP false
+#define FR_UNIT_WR true
+#elif defined(FR_COOP_LP_UNIT)
+#define FR_COOP_K fr_coop_lp_kernel
+#define FR_COOP_XK fr_coop_x_lp_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR false
 #else
+#define FR_COOP_K fr_coop_kernel
+#define FR_COOP_XK fr_coop_x_kernel
+#define FR_UNIT_LP false
+#define FR_UNIT_WR false
+#endif
 template <int CK, bool EN, int WPB, bool KC>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_lp_kernel(FrRolloutArgs a)
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void FR_COOP_K(FrRolloutArgs a)
 {
-    constexpr bool LP = true;
+    constexpr bool LP = FR_UNIT_LP, WR = FR_UNIT_WR;
 #include "fr_coop_kernel_body.inc"
 }
-#endif
 
 
 // The update's launch: four waves of main rows per workgroup (rollouts [0, xbase)) and four more
@@ -2263,21 +2326,12 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))
 // extra rows [xbase, count) plus the folded filter() row, xrows of them, four per workgroup) those
 // four waves first carry the rows left over through the horizon, a quarter each (relay_stage).
 constexpr int XW = 8;
-#ifndef FR_COOP_LP_UNIT
 template <int CK, bool EN>
-__global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_x_kernel(FrRolloutArgs a)
+__global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void FR_COOP_XK(FrRolloutArgs a)
 {
-    constexpr bool LP = false;
+    constexpr bool LP = FR_UNIT_LP, WR = FR_UNIT_WR;
 #include "fr_coop_x_kernel_body.inc"
 }
-#else
-template <int CK, bool EN>
-__global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_coop_x_lp_kernel(FrRolloutArgs a)
-{
-    constexpr bool LP = true;
-#include "fr_coop_x_kernel_body.inc"
-}
-#endif
 
 namespace mppi_eng {
 
@@ -2294,19 +2348,16 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
     return at.sharedSizeBytes >= want ? 0u : (unsigned)(want - at.sharedSizeBytes);
 }
 
-// The kinematic link-position model's launches (fr_coop_lp.hip): the x kernel, and fr_coop_lp_kernel
-// with wpb waves per workgroup and compact or 768-B records
-void launch_fr_coop_lp_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);
-void launch_fr_coop_lp_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact);
-bool fr_coop_lp_is_update_kernel(const void *func);   // an fr_coop_x_lp_kernel instantiation
-
-#ifdef FR_COOP_LP_UNIT
-#define FR_COOP_K fr_coop_lp_kernel
-#define FR_COOP_XK fr_coop_x_lp_kernel
-#else
-#define FR_COOP_K fr_coop_kernel
-#define FR_COOP_XK fr_coop_x_kernel
-#endif
+// The variant units' launches (fr_coop_lp.hip, fr_coop_wr.hip, fr_coop_wr_lp.hip): the x kernel, and
+// the unit's fr_coop_*_kernel with wpb waves per workgroup and compact or 768-B records
+#define FR_UNIT_DECL(tag)                                                                                     \
+    void launch_fr_coop_##tag##_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);                        \
+    void launch_fr_coop_##tag##_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact); \
+    bool fr_coop_##tag##_is_update_kernel(const void *func);   /* an x-kernel instantiation of the unit */
+FR_UNIT_DECL(lp)
+FR_UNIT_DECL(wr)
+FR_UNIT_DECL(wr_lp)
+#undef FR_UNIT_DECL
 
 template <int CK, bool EN, int WPB, bool KC>
 static void launch_k(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
@@ -2325,7 +2376,8 @@ static void launch_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-#ifndef FR_COOP_LP_UNIT
+#ifndef FR_COOP_VARIANT_UNIT
+    if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_one(a, nb, s, WPB, KC) : launch_fr_coop_wr_one(a, nb, s, WPB, KC);
     if (a.link_positions) return launch_fr_coop_lp_one(a, nb, s, WPB, KC);
 #endif
     if (a.cost_kind == CK_TRACK_POINT) launch_k<CK_TRACK_POINT, false, WPB, KC>(a, nb, s);
@@ -2335,7 +2387,8 @@ static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 
 static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-#ifndef FR_COOP_LP_UNIT
+#ifndef FR_COOP_VARIANT_UNIT
+    if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_x(a, nb, s) : launch_fr_coop_wr_x(a, nb, s);
     if (a.link_positions) return launch_fr_coop_lp_x(a, nb, s);
 #endif
     if (a.cost_kind == CK_TRACK_POINT) launch_x<CK_TRACK_POINT, false>(a, nb, s);
@@ -2343,21 +2396,28 @@ static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
     else launch_x<CK_ASSISTED_MANIPULATION, false>(a, nb, s);
 }
 
-#ifdef FR_COOP_LP_UNIT
-void launch_fr_coop_lp_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s) { launch_x_any(a, nb, s); }
+#ifdef FR_COOP_VARIANT_UNIT
+#if defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
+#define FR_UNIT_FN(pre, post) pre##wr_lp##post
+#elif defined(FR_COOP_WR_UNIT)
+#define FR_UNIT_FN(pre, post) pre##wr##post
+#else
+#define FR_UNIT_FN(pre, post) pre##lp##post
+#endif
+void FR_UNIT_FN(launch_fr_coop_, _x)(const FrRolloutArgs &a, unsigned nb, hipStream_t s) { launch_x_any(a, nb, s); }
 
-void launch_fr_coop_lp_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact)
+void FR_UNIT_FN(launch_fr_coop_, _one)(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact)
 {
     if (wpb == 4) launch_one<4, true>(a, nb, s);   // (the four-wave launch writes compact records only)
     else if (compact) launch_one<1, true>(a, nb, s);
     else launch_one<1, false>(a, nb, s);
 }
 
-bool fr_coop_lp_is_update_kernel(const void *f)
+bool FR_UNIT_FN(fr_coop_, _is_update_kernel)(const void *f)
 {
-    return f == (const void *)&fr_coop_x_lp_kernel<CK_ASSISTED_MANIPULATION, false> ||
-           f == (const void *)&fr_coop_x_lp_kernel<CK_ASSISTED_MANIPULATION, true> ||
-           f == (const void *)&fr_coop_x_lp_kernel<CK_TRACK_POINT, false>;
+    return f == (const void *)&FR_COOP_XK<CK_ASSISTED_MANIPULATION, false> ||
+           f == (const void *)&FR_COOP_XK<CK_ASSISTED_MANIPULATION, true> ||
+           f == (const void *)&FR_COOP_XK<CK_TRACK_POINT, false>;
 }
 #else
 
@@ -2388,7 +2448,8 @@ bool fr_coop_is_update_kernel(const void *f)
 {
     return f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, false> ||
            f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
-           f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f);
+           f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f) ||
+           fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f);
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at
@@ -2442,6 +2503,6 @@ hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const CoopPlan &p, hipS
     return hipGetLastError();
 }
 
-#endif   // FR_COOP_LP_UNIT
+#endif   // FR_COOP_VARIANT_UNIT
 
 }  // namespace mppi_eng

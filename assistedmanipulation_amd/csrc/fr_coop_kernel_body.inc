@@ -1,6 +1,7 @@
 // fr_coop_kernel_body.inc - the body of fr_coop_kernel and fr_coop_lp_kernel (fr_coop.hip), which
 // differ in the objective alone: LP (a constexpr bool of the including kernel) selects the kinematic
-// link-position model's.  Text shared by inclusion, so the default mode's kernels compile from the
+// link-position model's; WR (likewise) the simulated end-effector
+// wrench in the rows' step (coop_rows).  Text shared by inclusion, so the default mode's kernels compile from the
 // very statements they always had.
     constexpr int KS = EN ? LDS_KIN_EN : LDS_KIN;
     __shared__ __attribute__((aligned(16))) double lds_kin[WPB * ROWS_PER_WAVE * KS];
@@ -24,8 +25,8 @@
             kept_rows_wave(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, rk);
         }
     }
-    coop_rows<CK, EN, false, 0, false, KC>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, lds_kin + wrow * KS,
-                                           lds_scr + wrow * LDS_SCR, Lmodel, Lx0);
+    coop_rows<CK, EN, false, 0, false, KC, WR>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, lds_kin + wrow * KS,
+                                               lds_scr + wrow * LDS_SCR, Lmodel, Lx0);
     if constexpr (WPB == 4) {
         if (a.costs_in_launch) launch_costs<CK, EN, KC, LP>(a, wv, lane, Lmodel);
     } else if constexpr (WPB == 1) {

@@ -1,5 +1,6 @@
 // fr_coop_x_kernel_body.inc - the body of fr_coop_x_kernel and fr_coop_x_lp_kernel (fr_coop.hip);
-// LP (a constexpr bool of the including kernel): the kinematic link-position model's objective.
+// LP (a constexpr bool of the including kernel): the kinematic link-position model's objective;
+// WR (likewise): the simulated end-effector wrench in the rows' step (coop_rows).
     constexpr int KS = EN ? LDS_KIN_EN : LDS_KIN;
     __shared__ __attribute__((aligned(16))) double lds_kin[5 * ROWS_PER_WAVE * KS];
     __shared__ __attribute__((aligned(16))) double lds_scr[5 * ROWS_PER_WAVE * LDS_SCR];
@@ -54,8 +55,8 @@
             __builtin_amdgcn_s_setprio(1);   // above the objective's waves, below the relay
         }
         const int wblk = blockIdx.x * 4 + wv;
-        coop_rows<CK, EN, false, 0, true>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, Lk, Lw, Lmodel, Lx0,
-                                          nullptr, 0, 0x7FFFFFFF, Lq + Q_PROG + wv);
+        coop_rows<CK, EN, false, 0, true, false, WR>(a, (int64_t)wblk * ROWS_PER_WAVE + rowi, lane, wblk, Lk, Lw, Lmodel, Lx0,
+                                                     nullptr, 0, 0x7FFFFFFF, Lq + Q_PROG + wv);
         __builtin_amdgcn_s_setprio(0);
         if (cil) {
             signal_records(Lflag + wv);
@@ -75,9 +76,9 @@
                 if (a.ahead_noise) group_draws(a, s, lane, Lflag);
                 cost_work<CK, EN, LP>(a, s, ng, lane, Lmodel, Lcs, Lflag, Lq, s);
             }
-            if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst, ahead);
+            if (relay) relay_stage<CK, EN, WR>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst, ahead);
         } else {
-            if (relay) relay_stage<CK, EN>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst);
+            if (relay) relay_stage<CK, EN, WR>(a, s, member, lane, Lk, Lw, Lmodel, Lx0, Lflag, Lq, Lst);
         }
         if (!cil) return;
         // the draws for main wave s's rows (relay stages made theirs before their stage; wave 0's

@@ -235,11 +235,27 @@ __device__ void solve_mass(const DevModel &M, const Bodies &B, const double *b, 
     }
 }
 
-// PinocchioDynamics::calculate() (pinocchio_dynamics.cpp:153-224) on the object
-__device__ void calculate(const DevModel &M, DevPinocchio &P)
+// PinocchioDynamics::calculate() (pinocchio_dynamics.cpp:153-224) on the object.
+// w (or null): the simulated end-effector wrench (f, m) of this step, a force and a moment at the
+// grasp frame's origin in world axes.  Its joint torque J_G(q)^T w, J_G the grasp frame's geometric
+// Jacobian at its own origin in world axes (Pinocchio's LOCAL_WORLD_ALIGNED), joins m_joint_torque
+// ahead of the NLE: with the world motion subspace S_j = (v_j; omega_j), tau_w,j = v_j . f +
+// omega_j . (m + p_ee x f) for the joints under the frame (bodies 0..9), 0 for the fingers.
+__device__ void calculate(const DevModel &M, DevPinocchio &P, const double *w = nullptr)
 {
     Bodies B;
     fk_bodies(M, P.q, B);
+    if (w) {
+        const double *R9 = B.R[FR_EE_PARENT], *p9 = B.p[FR_EE_PARENT];
+        double pe[3], mo[3];
+        for (int r = 0; r < 3; r++) pe[r] = p9[r] + ((R9[3 * r] * M.ee_p[0] + R9[3 * r + 1] * M.ee_p[1]) + R9[3 * r + 2] * M.ee_p[2]);
+        cross3(pe, w, mo);
+        for (int r = 0; r < 3; r++) mo[r] = w[3 + r] + mo[r];
+        for (int i = 0; i <= FR_EE_PARENT; i++) {
+            const double *S = B.S[i];
+            P.tau[i] += ((S[0] * w[0] + S[1] * w[1]) + S[2] * w[2]) + ((S[3] * mo[0] + S[4] * mo[1]) + S[5] * mo[2]);
+        }
+    }
     const double zero[FR_NB] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double nle[FR_NB], V[FR_NB][6];
     rnea(M, B, P.v, zero, M.gravity, nle, V);
@@ -329,14 +345,14 @@ __device__ void set_state(const DevModel &M, DevPinocchio &P, const double *x, d
     calculate(M, P);
 }
 
-__device__ void step(const DevModel &M, DevPinocchio &P, const double *u, double dt)
+__device__ void step(const DevModel &M, DevPinocchio &P, const double *u, double dt, const double *w = nullptr)
 {
     const double yaw = P.q[2], c = cos(yaw), s = sin(yaw);
     P.v[0] = c * u[0] + (-s) * u[1];   // Rotation2Dd(yaw) * base_velocity (:234)
     P.v[1] = s * u[0] + c * u[1];
     P.v[2] = u[2];
     for (int i = 0; i < FR_NB; i++) P.tau[i] = (i >= 3 && i < 10) ? u[i] : 0.0;   // segment<ARM>(BASE)
-    calculate(M, P);
+    calculate(M, P, w);   // tau = (0, 0, 0, u_arm, 0, 0) + J_G^T w, then += NLE
     for (int i = 0; i < FR_NB; i++) P.v[i] = P.v[i] + P.a[i] * dt;
     for (int i = 0; i < FR_NB; i++) P.q[i] = P.q[i] + P.v[i] * dt;
     double power = 0.0;
@@ -365,7 +381,7 @@ __global__ __launch_bounds__(64) void fr_object_kernel(ObjArgs a)
     if (a.op == OBJ_SET_STATE) {
         set_state(M, P, a.x, a.time);
     } else if (a.op == OBJ_STEP) {
-        step(M, P, a.u, a.dt);
+        step(M, P, a.u, a.dt, a.has_wrench ? a.w : nullptr);
     } else if (a.op == OBJ_FORECAST) {
         set_state(M, P, a.x, a.time);
         const double zero[FR_C] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // Control::Zero()
@@ -377,7 +393,16 @@ __global__ __launch_bounds__(64) void fr_object_kernel(ObjArgs a)
             o[MPPI_DF_EXTERNAL_POWER] = 0.0;   // get_external_power (.hpp:220-223)
             o[MPPI_DF_ENERGY] = P.energy;
             for (int i = 0; i < 6; i++) o[MPPI_DF_WRENCH + i] = a.wrench ? a.wrench[k * 6 + i] : 0.0;
-            step(M, P, zero, a.dt);   // add_end_effector_simulated_wrench is a no-op (.hpp:276)
+            if (a.wrench_rows || (k == 0 && a.has_wrench)) {
+                // add_end_effector_simulated_wrench(forecast(t_k)) (dynamics.cpp:127) onto what
+                // the caller added before the call, which the first step consumes
+                double w[6];
+                for (int i = 0; i < 6; i++)
+                    w[i] = ((k == 0 && a.has_wrench) ? a.w[i] : 0.0) + ((a.wrench_rows && a.wrench) ? a.wrench[k * 6 + i] : 0.0);
+                step(M, P, zero, a.dt, w);
+            } else {
+                step(M, P, zero, a.dt);   // the reference's stub: add_end_effector_simulated_wrench is a no-op (.hpp:276)
+            }
         }
     } else if (a.op == OBJ_COST) {
         // get_cost(state, control, dynamics, time): the state's q / qd, the object's cached

@@ -118,6 +118,11 @@ struct FinishArgs {
     double *wait_local;
 };
 
+// The simulated end-effector wrench's rows of an update: [H][FR_WRENCH_ROW] doubles (six used: force,
+// moment), written by launch_wrench_table behind the H StepConst of the same buffer (a row is as
+// large as a StepConst), so that whatever reads an update's step constants finds its wrench rows.
+constexpr int FR_WRENCH_ROW = 8;
+static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows behind the step constants");
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -171,6 +176,11 @@ struct FrRolloutArgs {
     // fr_coop_x_kernel: the rows left over travel through four relay stages (fr_coop.hip
     // relay_stage; MPPI_HANDOVER=0 keeps them on one wave beside main wave 0)
     int handover;
+    // the simulated end-effector wrench (mppi_set_simulated_wrench; read by the host's launch
+    // selection only): the launches' step adds J_G^T w_k (fr_coop.hip's *_wr_kernel), w_k row k of
+    // the wrench table behind the step constants (steps + H, fsteps + H: FR_WRENCH_ROW doubles a
+    // row).  In the padding behind handover, like link_positions.
+    int simulated_wrench;
     // sharded over RCCL: the rank's slot R of the cost vector the engine all-reduces, to which every
     // in-launch wait that gives up adds 1 (so every rank's finish kernel sees any rank's), or null
     double *wait_sum;
@@ -387,8 +397,25 @@ struct ObjArgs {
     DevCost cost;         // cost: the objective
     StepConst sc;         // cost: trajectory_cost's constants of the wrench at `time`
     int link_positions;   // cost: the self-collision term on the object's cached link positions (kinematic model)
+    // step / forecast: the simulated end-effector wrench (force, moment at the grasp frame's origin,
+    // world axes) summed by add_end_effector_simulated_wrench since the last step; has_wrench = 0
+    // runs the step without the term.  forecast with wrench_rows: row k of `wrench` is added before step k
+    double w[6];
+    int has_wrench, wrench_rows;
 };
 hipError_t launch_fr_object(const ObjArgs &a, hipStream_t s);
+// The update's simulated-wrench rows, out[H][FR_WRENCH_ROW]: source WT_CONST the wrench w in every row,
+// WT_TABLE row k of table[H][6], WT_FORECAST forecast(t0 + k dt) as the step constants sample it
+enum WrenchSource : int { WT_CONST = 0, WT_TABLE = 1, WT_FORECAST = 2 };
+struct WrenchTableArgs {
+    ForecastArgs f;
+    int source, H;
+    double w[6];
+    const double *table;
+    double t0, dt;
+    double *out;
+};
+hipError_t launch_wrench_table(const WrenchTableArgs &a, hipStream_t s);
 // forecast(t0 + k dt) for k < steps into out[steps][6] (mppi_forecast_table)
 hipError_t launch_forecast_table(const ForecastArgs &f, double t0, double dt, int64_t steps, double *out, hipStream_t s);
 hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s);

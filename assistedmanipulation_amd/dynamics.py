@@ -54,18 +54,22 @@ class PinocchioDynamicsObject:
     STATE_DOF = abi.MPPI_FR_STATE
     CONTROL_DOF = abi.MPPI_FR_CONTROL
 
-    def __init__(self, handle, descriptor, link_positions=None):
+    def __init__(self, handle, descriptor, link_positions=None, simulated_wrench=None):
         self._L = load()
         self._h = handle
         self._desc = descriptor
         self._link_positions = link_positions
         if link_positions is not None:
             self.set_link_positions(abi.MPPI_LINK_POSITIONS_KINEMATIC if link_positions else abi.MPPI_LINK_POSITIONS_ZERO)
+        if simulated_wrench is not None:
+            self.set_simulated_wrench(abi.MPPI_SIMULATED_WRENCH_ON if simulated_wrench else abi.MPPI_SIMULATED_WRENCH_OFF)
 
     @staticmethod
-    def create(initial_state, model=None, device=0, link_positions=None):
+    def create(initial_state, model=None, device=0, link_positions=None, simulated_wrench=None):
         """`link_positions`: True the kinematic link-position model, False the reference's stub,
-        None what MPPI_LINK_POSITIONS says (unset: the stub)."""
+        None what MPPI_LINK_POSITIONS says (unset: the stub).  `simulated_wrench`: True forecast()
+        applies its wrench rows, False it only copies them (the reference's stub), None what
+        MPPI_SIMULATED_WRENCH says (unset: the stub)."""
         from .trajectory import EngineError, FrankaRidgebackDynamics
         L = load()
         desc = FrankaRidgebackDynamics(model).descriptor()
@@ -76,7 +80,7 @@ class PinocchioDynamicsObject:
         st = L.mppi_dynamics_create(C.byref(desc), _p(x), int(device), C.byref(h))
         if st != abi.MPPI_OK:
             raise EngineError(st, L.mppi_last_error(None).decode())
-        return PinocchioDynamicsObject(h, desc, link_positions)
+        return PinocchioDynamicsObject(h, desc, link_positions, simulated_wrench)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -100,7 +104,8 @@ class PinocchioDynamicsObject:
 
     def copy(self):
         """mppi::Dynamics::copy (mppi.hpp:47): a new object at this one's state."""
-        return PinocchioDynamicsObject.create(self.get_state(), link_positions=self._link_positions)
+        return PinocchioDynamicsObject.create(self.get_state(), link_positions=self._link_positions,
+                                              simulated_wrench=self.simulated_wrench)
 
     def set_state(self, state, time):
         x = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
@@ -133,6 +138,31 @@ class PinocchioDynamicsObject:
         """mppi_dynamics_set_link_positions (abi.MPPI_LINK_POSITIONS_*); evaluate_cost follows it."""
         self._check(self._L.mppi_dynamics_set_link_positions(self._h, int(mode)))
         self._link_positions = int(mode) == abi.MPPI_LINK_POSITIONS_KINEMATIC
+
+    def add_end_effector_simulated_wrench(self, wrench):
+        """PinocchioDynamics::add_end_effector_simulated_wrench: a force and a moment at the grasp
+        frame's origin in world axes (6), cumulative; the next step applies the sum and zeroes it."""
+        w = np.ascontiguousarray(wrench, dtype=np.float64).reshape(-1)
+        assert w.size == 6
+        self._check(self._L.mppi_dynamics_add_end_effector_simulated_wrench(self._h, _p(w)))
+
+    def get_end_effector_simulated_wrench(self):
+        """The wrench the last step applied (6); zeros before any step."""
+        o = np.zeros(6)
+        self._check(self._L.mppi_dynamics_get_end_effector_simulated_wrench(self._h, _p(o)))
+        return o
+
+    def set_simulated_wrench(self, mode):
+        """mppi_dynamics_set_simulated_wrench (abi.MPPI_SIMULATED_WRENCH_OFF / _ON): whether
+        forecast() adds its wrench rows before each step."""
+        self._check(self._L.mppi_dynamics_set_simulated_wrench(self._h, int(mode)))
+
+    @property
+    def simulated_wrench(self):
+        """Whether forecast() applies its wrench rows (mppi_dynamics_get_simulated_wrench)."""
+        m = C.c_int(0)
+        self._check(self._L.mppi_dynamics_get_simulated_wrench(self._h, C.byref(m)))
+        return m.value == abi.MPPI_SIMULATED_WRENCH_ON
 
     def link_positions(self):
         """get_link_position of every Link (abi.LINK_NAMES order) after the last call, (13, 3): the

@@ -68,11 +68,20 @@ class FrankaRidgebackDynamics(Dynamics):
     `link_positions`: what get_link_position answers in the rollouts (mppi_set_link_positions) -
     True the kinematic model (the links' body-frame translations of the last calculate(), a live
     self-collision term), False the reference's stub (zeros), None what MPPI_LINK_POSITIONS says
-    (unset: the stub)."""
+    (unset: the stub).
+    `simulated_wrench`: the end-effector wrench the rollouts' dynamics feel
+    (mppi_set_simulated_wrench) - "state" the wrench slots of the update's state at every step,
+    "forecast" row k of the forecast the objective reads at step k, False none (the reference's
+    stub), None what MPPI_SIMULATED_WRENCH says (unset: none)."""
     control_dof = abi.MPPI_FR_CONTROL
     state_dof = abi.MPPI_FR_STATE
+    SIMULATED_WRENCH_MODES = {False: abi.MPPI_SIMULATED_WRENCH_OFF, "state": abi.MPPI_SIMULATED_WRENCH_STATE,
+                              "forecast": abi.MPPI_SIMULATED_WRENCH_FORECAST}
 
-    def __init__(self, model=None, link_positions=None):
+    def __init__(self, model=None, link_positions=None, simulated_wrench=None):
+        if simulated_wrench is not None and simulated_wrench not in self.SIMULATED_WRENCH_MODES:
+            raise ValueError('simulated_wrench must be None, False, "state" or "forecast"')
+        self.simulated_wrench = simulated_wrench
         if model is None:
             model = abi.mppi_frankaridgeback_desc()
             load().mppi_default_frankaridgeback(C.byref(model))
@@ -238,6 +247,9 @@ class Trajectory:
         lp = getattr(dynamics, "link_positions", None)
         if lp is not None:   # FrankaRidgebackDynamics(link_positions=...)
             t.set_link_positions(abi.MPPI_LINK_POSITIONS_KINEMATIC if lp else abi.MPPI_LINK_POSITIONS_ZERO)
+        sw = getattr(dynamics, "simulated_wrench", None)
+        if sw is not None:   # FrankaRidgebackDynamics(simulated_wrench=...)
+            t.set_simulated_wrench(FrankaRidgebackDynamics.SIMULATED_WRENCH_MODES[sw])
         return t
 
     # -- lifecycle --------------------------------------------------------------------------
@@ -287,6 +299,22 @@ class Trajectory:
             return False
         self._check(st)
         return m.value == abi.MPPI_LINK_POSITIONS_KINEMATIC
+
+    def set_simulated_wrench(self, mode):
+        """mppi_set_simulated_wrench: abi.MPPI_SIMULATED_WRENCH_OFF / _STATE / _FORECAST;
+        FrankaRidgeback handles, before the first update."""
+        self._check(self._L.mppi_set_simulated_wrench(self._h, int(mode)))
+
+    @property
+    def simulated_wrench(self):
+        """The rollouts' simulated-wrench mode (abi.MPPI_SIMULATED_WRENCH_*, read-only;
+        MPPI_SIMULATED_WRENCH_OFF for a handle without the FrankaRidgeback dynamics)."""
+        m = C.c_int(0)
+        st = self._L.mppi_get_simulated_wrench(self._h, C.byref(m))
+        if st == abi.MPPI_ERR_UNSUPPORTED:
+            return abi.MPPI_SIMULATED_WRENCH_OFF
+        self._check(st)
+        return m.value
 
     def set_noise_source(self, source, seed=0x5EED):
         self._check(self._L.mppi_set_noise_source(self._h, int(source), int(seed)))

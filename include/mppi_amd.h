@@ -371,6 +371,34 @@ const char *mppi_link_name(int link);
 mppi_status mppi_set_link_positions(mppi_handle *h, int mode);
 mppi_status mppi_get_link_positions(mppi_handle *h, int *mode);
 
+/* The simulated end-effector wrench: the push the rollouts' robot feels (the reference leaves
+ * PinocchioDynamics::add_end_effector_simulated_wrench an empty body, pinocchio_dynamics.hpp:247-276).
+ * A wrench w = (f, m) is a force and a moment at the origin of the grasp frame (panda_grasp_joint)
+ * in world axes.  Its joint torque is tau_w = J_G(q)^T w, J_G the geometric Jacobian of the grasp
+ * frame at its own origin in world axes (Pinocchio's LOCAL_WORLD_ALIGNED): column j is
+ * (a_j x (p_ee - p_j); a_j) for a revolute joint under the frame and (a_j; 0) for a prismatic one,
+ * zero for the two fingers; q is the configuration the step's own calculate() runs at.  The step is
+ * tau = (0, 0, 0, u_arm, 0, 0) + tau_w, then calculate() as before (tau += NLE, qdd = M^-1 (u_arm +
+ * tau_w)): the base joints take their tau_w too, and the tank's power is (u + tau_w + NLE) . v_new.
+ * The external power stays 0.  (Not the Jacobian of the reference's commented-out line,
+ * pinocchio_dynamics.cpp:237-240, which is the WORLD one with its corner overwritten; the objective
+ * keeps reading that one.)
+ * OFF (the default): the reference's stub, no term.  STATE: the six wrench slots of the update's
+ * state, x[24..30), at every step.  FORECAST: at step k, row k of the forecast the objective reads
+ * for that update - the mppi_set_forecast table, or the attached forecast at t0 + k dt; zeros without
+ * either.  mppi_set_simulated_wrench: FrankaRidgeback handles only (MPPI_ERR_UNSUPPORTED otherwise),
+ * before the first update (MPPI_ERR_INVALID after it, and for an unknown mode).  The environment
+ * variable MPPI_SIMULATED_WRENCH=0|1|2 (anything else fails the create with MPPI_ERR_INVALID) sets
+ * the mode new handles start in, and new dynamics objects' forecast mode (0: OFF, 1 or 2: ON).
+ * Sharded handles take the mode per handle: every rank must set the same one.  Added after ABI
+ * version 5 without a version change (no struct changed): detect by symbol. */
+#define MPPI_SIMULATED_WRENCH_OFF 0
+#define MPPI_SIMULATED_WRENCH_STATE 1
+#define MPPI_SIMULATED_WRENCH_FORECAST 2
+#define MPPI_SIMULATED_WRENCH_ON 1   /* the dynamics object's forecast mode */
+mppi_status mppi_set_simulated_wrench(mppi_handle *h, int mode);
+mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode);
+
 /* Phase-split update for callers that run the collectives themselves (multi-GPU with an
  * external communicator, or two shards on one device in tests).  Between phase 1 and 2 the
  * caller all-reduces (sum) the R + 1 doubles of mppi_device_costs(h) - the R costs and slot R,
@@ -594,6 +622,16 @@ mppi_status mppi_cost_evaluate(const mppi_cost_desc *cost, mppi_dynamics *d, con
  * the zero mode. */
 mppi_status mppi_dynamics_set_link_positions(mppi_dynamics *d, int mode);
 mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out);
+/* add_end_effector_simulated_wrench (6 doubles: force, moment; semantics above): cumulative; the
+ * next mppi_dynamics_step applies the sum and zeroes it.  get_end_effector_simulated_wrench: the
+ * wrench the last step applied, zeros before any step. */
+mppi_status mppi_dynamics_add_end_effector_simulated_wrench(mppi_dynamics *d, const double *wrench6);
+mppi_status mppi_dynamics_get_end_effector_simulated_wrench(mppi_dynamics *d, double *out6);
+/* Whether mppi_dynamics_forecast adds row k of its `wrench` before step k, as dynamics.cpp:127 does
+ * (MPPI_SIMULATED_WRENCH_ON), or only copies the rows into its output (_OFF, the default and the
+ * reference's stub).  An explicit add is live in either mode. */
+mppi_status mppi_dynamics_set_simulated_wrench(mppi_dynamics *d, int mode);
+mppi_status mppi_dynamics_get_simulated_wrench(mppi_dynamics *d, int *mode);
 /* forecast(t0 + k dt) for k < steps of the handle's attached forecast (steps x 6). */
 mppi_status mppi_forecast_table(mppi_handle *h, double t0, double dt, int64_t steps, double *out);
 

@@ -123,6 +123,9 @@ public:
     // the link-position model the rollouts of a trajectory on this dynamics use
     // (MPPI_LINK_POSITIONS_*), or -1: the handle's own (the stub, or what MPPI_LINK_POSITIONS says)
     virtual int link_positions() const { return -1; }
+    // the simulated end-effector wrench of those rollouts (MPPI_SIMULATED_WRENCH_*), or -1: the
+    // handle's own (off, or what MPPI_SIMULATED_WRENCH says)
+    virtual int simulated_wrench() const { return -1; }
 };
 class DeviceCost {
 public:
@@ -214,6 +217,11 @@ public:
             mppi_destroy(h);
             return nullptr;
         }
+        if (ddev->simulated_wrench() >= 0 && mppi_set_simulated_wrench(h, ddev->simulated_wrench()) != MPPI_OK) {
+            std::cerr << mppi_last_error(nullptr) << std::endl;
+            mppi_destroy(h);
+            return nullptr;
+        }
         return std::unique_ptr<Trajectory>(new Trajectory(h, configuration, std::move(dynamics), std::move(cost)));
     }
 
@@ -223,6 +231,19 @@ public:
     {
         int mode = MPPI_LINK_POSITIONS_ZERO;
         return mppi_get_link_positions(m_h, &mode) == MPPI_OK && mode == MPPI_LINK_POSITIONS_KINEMATIC;
+    }
+    // the rollouts' simulated end-effector wrench (MPPI_SIMULATED_WRENCH_*): set before the first
+    // update (mppi_set_simulated_wrench; false and a message on stderr otherwise)
+    bool set_simulated_wrench(int mode)
+    {
+        if (mppi_set_simulated_wrench(m_h, mode) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    int simulated_wrench() const
+    {
+        int mode = MPPI_SIMULATED_WRENCH_OFF;
+        return mppi_get_simulated_wrench(m_h, &mode) == MPPI_OK ? mode : MPPI_SIMULATED_WRENCH_OFF;
     }
     Trajectory(const Trajectory &) = delete;
     Trajectory &operator=(const Trajectory &) = delete;
@@ -372,6 +393,22 @@ private:
 
 namespace FrankaRidgeback {
 
+// A wrench (force, moment) as the reference passes it (dynamics.hpp: Vector6d).
+#if __has_include(<Eigen/Dense>)
+using Vector6d = Eigen::Matrix<double, 6, 1>;
+#else
+struct Vector6d {
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    static Vector6d Zero() { return Vector6d{}; }
+    double *data() { return v; }
+    const double *data() const { return v; }
+    double &operator[](std::ptrdiff_t i) { return v[i]; }
+    double operator[](std::ptrdiff_t i) const { return v[i]; }
+    double &operator()(std::ptrdiff_t i) { return v[i]; }
+    double operator()(std::ptrdiff_t i) const { return v[i]; }
+};
+#endif
+
 // EndEffectorState (dynamics.hpp:95-117); orientation as (x, y, z, w) and as a row-major matrix.
 struct EndEffectorState {
     double position[3];
@@ -429,6 +466,11 @@ public:
         // Trajectory created on this dynamics.  false: the handle's default (the reference's stub,
         // zeros, unless MPPI_LINK_POSITIONS=1)
         bool link_positions = false;
+        // the simulated end-effector wrench (mppi_set_simulated_wrench) of the rollouts of a
+        // Trajectory created on this dynamics, MPPI_SIMULATED_WRENCH_OFF / _STATE / _FORECAST; any
+        // mode but OFF also makes this object's forecast apply its wrench rows.  -1: the handle's
+        // default (off, unless MPPI_SIMULATED_WRENCH says otherwise)
+        int simulated_wrench = -1;
     };
     // wrench forecast(time) of the dynamics' forecast handle (DynamicsForecast::Handle), or none
     using WrenchSource = std::function<bool(double time, double *wrench6)>;
@@ -500,7 +542,21 @@ public:
     double get_tank_energy() { return query(48, 1)[0]; }
     double get_joint_power() const { return 0.0; }       // pinocchio_dynamics.hpp:211-214
     double get_external_power() const { return 0.0; }    // :220-223
-    void add_end_effector_simulated_wrench(const double *) {}   // :276 (a no-op)
+    // :247-276, the reference's todo: a force and a moment at the grasp frame's origin in world
+    // axes, cumulative until the next step applies the sum (mppi_amd.h, the simulated wrench)
+    void add_end_effector_simulated_wrench(Vector6d wrench)
+    {
+        check(mppi_dynamics_add_end_effector_simulated_wrench(object(), wrench.data()));
+    }
+    // the wrench the last step applied (zeros before any step); the object is created on first use,
+    // like every query here, so the method is const in the reference's sense only
+    Vector6d get_end_effector_simulated_wrench() const
+    {
+        Vector6d w = Vector6d::Zero();
+        check(mppi_dynamics_get_end_effector_simulated_wrench(const_cast<PinocchioDynamics *>(this)->object(), w.data()));
+        return w;
+    }
+    int simulated_wrench() const override { return m_configuration.simulated_wrench; }
     void set_forecast(WrenchSource source) { m_forecast = std::move(source); }
     const WrenchSource &get_forecast() const { return m_forecast; }
 
@@ -517,6 +573,9 @@ public:
             describe(d);
             check(mppi_dynamics_create(&d, x0.data(), m_configuration.device, &m_obj));
             if (m_configuration.link_positions) check(mppi_dynamics_set_link_positions(m_obj, MPPI_LINK_POSITIONS_KINEMATIC));
+            if (m_configuration.simulated_wrench >= 0)
+                check(mppi_dynamics_set_simulated_wrench(m_obj, m_configuration.simulated_wrench != MPPI_SIMULATED_WRENCH_OFF
+                                                                    ? MPPI_SIMULATED_WRENCH_ON : MPPI_SIMULATED_WRENCH_OFF));
         }
         return m_obj;
     }
