@@ -18,6 +18,7 @@ from .trajectory import (AssistedManipulation, Cost, Dynamics, EngineError, Trac
                          FrankaRidgebackDynamics, PointMassDynamics, Predicted, QuadraticCost, Trajectory,
                          comm_unique_id, shard_range)
 
+from .obstacles import HalfSpaceObstacle, ObstacleAvoidance, SphereObstacle, obstacle_clearance  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
 from .dynamics import DynamicsForecast, EndEffectorState, PinocchioDynamicsObject, evaluate_cost  # noqa: E402
 
@@ -27,5 +28,6 @@ __all__ = [
     "huddled_state", "point_mass_configuration", "locf_forecast_configuration", "average_forecast_configuration",
     "kalman_forecast_configuration", "AssistedManipulation", "TrackPoint", "Cost", "Dynamics",
     "EngineError", "FrankaRidgebackDynamics", "PointMassDynamics", "QuadraticCost", "Trajectory",
-    "comm_unique_id", "shard_range", "Predicted",
+    "comm_unique_id", "shard_range", "Predicted", "ObstacleAvoidance", "SphereObstacle", "HalfSpaceObstacle",
+    "obstacle_clearance",
 ]

@@ -98,6 +98,14 @@ PROTOTYPES = {
     "mppi_dynamics_get_end_effector_simulated_wrench": (C.c_int, [_h, _dp]),
     "mppi_dynamics_set_simulated_wrench": (C.c_int, [_h, C.c_int]),
     "mppi_dynamics_get_simulated_wrench": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_default_obstacle_config": (None, [C.POINTER(abi.mppi_obstacle_config)]),
+    "mppi_set_obstacle_avoidance": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config)]),
+    "mppi_get_obstacle_avoidance": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_obstacle_config)]),
+    "mppi_set_obstacles": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle), C.c_int32, C.c_double]),
+    "mppi_get_obstacles": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mppi_optimal_obstacle_cost": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_obstacle_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_obstacle), C.c_int32,
+                                              C.c_double, _dp]),
 }
 
 _lib = None

@@ -64,6 +64,12 @@ MPPI_SIMULATED_WRENCH_OFF = 0
 MPPI_SIMULATED_WRENCH_STATE = 1
 MPPI_SIMULATED_WRENCH_FORECAST = 2
 MPPI_SIMULATED_WRENCH_ON = 1
+# mppi_set_obstacle_avoidance / mppi_set_obstacles
+MPPI_MAX_OBSTACLES = 16
+MPPI_OBSTACLE_POINTS = 9
+MPPI_OBSTACLE_SPHERE = 0
+MPPI_OBSTACLE_HALF_SPACE = 1
+MPPI_OBSTACLE_MASK_ALL = 0x1FF
 # One row of mppi_predicted_optimal / mppi_predicted_rollouts (MPPI_PRED_*): q_k, qd_k, the tank level,
 # then the grasp-frame, arm-mount and link positions at q_k
 MPPI_PRED_Q, MPPI_PRED_QD, MPPI_PRED_ENERGY, MPPI_PRED_EE, MPPI_PRED_ARM_MOUNT, MPPI_PRED_LINKS = 0, 12, 24, 25, 28, 31
@@ -150,6 +156,15 @@ class mppi_quadratic(C.Structure):
 
 class mppi_barrier(C.Structure):
     _fields_ = [("bound", _d), ("scale", _d), ("maximum_cost", _d)]
+
+
+class mppi_obstacle(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("mask", C.c_uint32), ("position", _d * 3), ("velocity", _d * 3), ("normal", _d * 3),
+                ("radius", _d)]
+
+
+class mppi_obstacle_config(C.Structure):
+    _fields_ = [("limit", mppi_barrier), ("radii", _d * MPPI_OBSTACLE_POINTS)]
 
 
 class mppi_assisted_manipulation_desc(C.Structure):

@@ -99,6 +99,90 @@ bool env_simulated_wrench(int &mode, std::string &why)
     return false;
 }
 
+// mppi_set_obstacle_avoidance's configuration: finite values, radii >= 0
+bool check_obstacle_config(const mppi_obstacle_config &c, std::string &why)
+{
+    if (!std::isfinite(c.limit.bound) || !std::isfinite(c.limit.scale) || !std::isfinite(c.limit.maximum_cost)) {
+        why = "obstacle avoidance: the barrier's bound, scale and max must be finite";
+        return false;
+    }
+    for (int i = 0; i < MPPI_OBSTACLE_POINTS; i++)
+        if (!std::isfinite(c.radii[i]) || c.radii[i] < 0.0) {
+            why = "obstacle avoidance: radii[" + std::to_string(i) + "] must be finite and >= 0";
+            return false;
+        }
+    return true;
+}
+
+// mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set
+bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why)
+{
+    if (count < 0 || count > MPPI_MAX_OBSTACLES) {
+        why = "obstacles: count must be in [0, " + std::to_string(MPPI_MAX_OBSTACLES) + "]";
+        return false;
+    }
+    if (count > 0 && !set) {
+        why = "obstacles: null set";
+        return false;
+    }
+    if (!std::isfinite(time)) {
+        why = "obstacles: the time must be finite";
+        return false;
+    }
+    for (int32_t o = 0; o < count; o++) {
+        const mppi_obstacle &b = set[o];
+        const std::string at = "obstacle " + std::to_string(o) + ": ";
+        if (b.kind != MPPI_OBSTACLE_SPHERE && b.kind != MPPI_OBSTACLE_HALF_SPACE) {
+            why = at + "unknown kind";
+            return false;
+        }
+        if (b.mask & ~MPPI_OBSTACLE_MASK_ALL) {
+            why = at + "mask has bits above bit 8";
+            return false;
+        }
+        bool finite = std::isfinite(b.radius);
+        for (int i = 0; i < 3; i++) finite = finite && std::isfinite(b.position[i]) && std::isfinite(b.velocity[i]) && std::isfinite(b.normal[i]);
+        if (!finite) {
+            why = at + "a value is not finite";
+            return false;
+        }
+        if (b.radius < 0.0) {
+            why = at + "negative radius";
+            return false;
+        }
+        if (b.kind == MPPI_OBSTACLE_HALF_SPACE) {
+            const double n = std::sqrt(b.normal[0] * b.normal[0] + b.normal[1] * b.normal[1] + b.normal[2] * b.normal[2]);
+            if (std::fabs(n - 1.0) > 1e-9) {
+                why = at + "the half-space normal is not of unit length";
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+// The device table of a configuration and a set at update time t0 (engine_types.hpp ObstacleTable)
+void fill_obstacle_table(ObstacleTable &t, const mppi_obstacle_config &c, const mppi_obstacle *set, int32_t count, double t0,
+                                double t_ref)
+{
+    t.limit = DevBarrier{c.limit.bound, c.limit.scale, c.limit.maximum_cost};
+    for (int i = 0; i < OB_POINTS; i++) t.radii[i] = c.radii[i];
+    t.t0 = t0;
+    t.t_ref = t_ref;
+    t.count = count;
+    for (int o = 0; o < count; o++) {
+        DevObstacle &d = t.ob[o];
+        for (int i = 0; i < 3; i++) {
+            d.position[i] = set[o].position[i];
+            d.velocity[i] = set[o].velocity[i];
+            d.normal[i] = set[o].normal[i];
+        }
+        d.radius = set[o].radius;
+        d.kind = set[o].kind == MPPI_OBSTACLE_HALF_SPACE ? OB_HALF_SPACE : OB_SPHERE;
+        d.mask = set[o].mask;
+    }
+}
+
 struct DeviceBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -153,9 +237,19 @@ struct mppi_handle {
     // mppi_set_simulated_wrench: MPPI_SIMULATED_WRENCH_OFF (the reference's stub), _STATE or
     // _FORECAST; fixed once the first update has run, like link_positions.  Each update writes its
     // wrench rows behind its step constants (d_steps + H, launch_wrench_table); the hipGraph path
-    // launches that ahead of the graph (wrench_ahead: phase 1 then leaves it out).
+    // launches that ahead of the graph (wrench_ahead: phase 1 then leaves it out, and the obstacle
+    // table with it).
     int simulated_wrench = MPPI_SIMULATED_WRENCH_OFF;
     bool wrench_ahead = false;
+    // mppi_set_obstacle_avoidance / mppi_set_obstacles: the configuration (fixed once enabled, before
+    // the first update, like link_positions) and the current set with its reference time.  Each
+    // update writes them with its own time behind its step constants and wrench rows (d_steps + 2 H,
+    // write_obstacle_table); the hipGraph path launches that ahead of the graph, like the wrench rows.
+    bool obstacle_avoidance = false;
+    mppi_obstacle_config ob_config{};
+    mppi_obstacle ob_set[MPPI_MAX_OBSTACLES] = {};
+    int32_t ob_count = 0;
+    double ob_time = 0.0;
     double *d_fc_rows = nullptr;    // [H][6] the caller's forecast table on the device (upload_steps)
     int64_t S = 0, K = 0, R = 0, H = 0, C = 0, X = 0;
     double dt = 0, gradient_step = 0, cost_scale = 0, gamma = 1;
@@ -944,6 +1038,28 @@ mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out)
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
+                                        int32_t count, double elapsed, double *cost)
+{
+    if (!d || !cost) return MPPI_ERR_INVALID;
+    if (d->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return dfail(d, MPPI_ERR_INVALID, "obstacle cost needs the kinematic link-position model (mppi_dynamics_set_link_positions)");
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    std::string why;
+    if (!check_obstacle_config(c, why) || !check_obstacles(obstacles, count, elapsed, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    ObstacleTable t{};
+    fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0);   // tau = elapsed
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(launch_fr_object_obstacles(d->d_obj, t, d->d_buf, d->stream));
+    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipStreamSynchronize(d->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_add_end_effector_simulated_wrench(mppi_dynamics *d, const double *wrench6)
 {
     if (!d || !wrench6) return MPPI_ERR_INVALID;
@@ -1158,8 +1274,9 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
     CREATE_TRY(dalloc(h, &h->d_rank, (size_t)h->R));
     CREATE_TRY(dalloc(h, &h->d_rank_keys, (size_t)rank_scratch(h->S)));
     CREATE_TRY(dalloc(h, &h->d_status, 1));
-    CREATE_TRY(dalloc(h, &h->d_steps_buf[0], (size_t)(2 * h->H)));   // (the second half: the wrench rows, zeros)
-    CREATE_TRY(dalloc(h, &h->d_steps_buf[1], (size_t)(2 * h->H)));
+    // (the second half: the wrench rows, zeros; behind them the update's obstacle table)
+    CREATE_TRY(dalloc(h, &h->d_steps_buf[0], (size_t)(2 * h->H + OB_TABLE_STEPS)));
+    CREATE_TRY(dalloc(h, &h->d_steps_buf[1], (size_t)(2 * h->H + OB_TABLE_STEPS)));
     CREATE_TRY(dalloc(h, &h->d_fc_rows, (size_t)(6 * h->H)));
     h->d_steps = h->d_steps_buf[0];
     CREATE_TRY(dalloc(h, &h->d_gamma, (size_t)h->H));
@@ -1664,6 +1781,13 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
     return c;
 }
 
+// FrRolloutArgs::link_positions of the handle's launches
+static int launch_link_mode(const mppi_handle *h)
+{
+    if (h->obstacle_avoidance) return FR_LINKS_OBSTACLES;
+    return h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? FR_LINKS_KINEMATIC : FR_LINKS_ZERO;
+}
+
 // filter() of the last update on the side stream, by itself (mppi.cpp:450-479)
 static mppi_status launch_filter_standalone(mppi_handle *h)
 {
@@ -1693,7 +1817,7 @@ static mppi_status launch_filter_standalone(mppi_handle *h)
         a.cost_kind = h->cost_kind;
         a.energy = h->cost_kind == MPPI_COST_ASSISTED_MANIPULATION && h->am.enable_energy_limit;
         a.rec = h->d_rec_opt;
-        a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
+        a.link_positions = launch_link_mode(h);
         a.simulated_wrench = h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF;   // (its update's rows: opt_steps + H)
         // the row's objective after its loop (fr_coop_kernel's one-wave path)
         a.costs_in_launch = fr_coop_costs_in_launch(h->env) ? 1 : 0;
@@ -1753,6 +1877,19 @@ static mppi_status write_wrench_rows(mppi_handle *h, const double *state, double
     return MPPI_OK;
 }
 
+// This update's obstacle table, behind its step constants and wrench rows.  The set and the time
+// change between updates, so the buffers alternate as they do for the wrench rows: the pending
+// filter() of the previous update reads the other one.  One small launch on the engine stream ahead
+// of the rollouts, the table by value.
+static mppi_status write_obstacle_table(mppi_handle *h, double time)
+{
+    h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
+    ObstacleTable t{};
+    fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time);
+    HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
 {
     if (!h || !state) return MPPI_ERR_INVALID;
@@ -1771,6 +1908,10 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
     }
     if (h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF && !h->wrench_ahead) {
         mppi_status st = write_wrench_rows(h, state, time);
+        if (st != MPPI_OK) return st;
+    }
+    if (h->obstacle_avoidance && !h->wrench_ahead) {
+        mppi_status st = write_obstacle_table(h, time);
         if (st != MPPI_OK) return st;
     }
 
@@ -1870,7 +2011,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         a.rx = h->d_rx;
         a.rtoken = ++h->relay_token ? h->relay_token : ++h->relay_token;   // (never 0)
         a.stage_work = h->env.stage_work_off ? 0 : 1;
-        a.link_positions = h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC;
+        a.link_positions = launch_link_mode(h);
         a.simulated_wrench = h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF;
         // sharded: this rank's wait timeouts into cost slot R, which the all-reduce carries to every rank
         a.wait_sum = h->comm ? h->d_costs_local + h->R : (sharded(h) ? h->d_costs + h->R : nullptr);
@@ -2330,6 +2471,13 @@ static mppi_status update_graph(mppi_handle *h, const double *state, double time
         mppi_status ws = write_wrench_rows(h, state, time);
         if (ws != MPPI_OK) return ws;
     }
+    // likewise the obstacle table: the current set and this update's time on every replay.  (Should
+    // the capture below fail, update_eager writes the same table into the same buffer once more: one
+    // redundant small launch on a path that runs at most once per handle.)
+    if (h->obstacle_avoidance) {
+        mppi_status ws = write_obstacle_table(h, time);
+        if (ws != MPPI_OK) return ws;
+    }
     if (capture) HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     else h->graph_dry = true;
     h->wrench_ahead = true;
@@ -2436,6 +2584,8 @@ mppi_status mppi_set_link_positions(mppi_handle *h, int mode)
         return fail(h, MPPI_ERR_INVALID, "link-position model must be MPPI_LINK_POSITIONS_ZERO or MPPI_LINK_POSITIONS_KINEMATIC");
     // the rollout launches' kernels are part of the launch plan and of a captured graph
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "the link-position model is set before the first update");
+    if (h->obstacle_avoidance && mode != MPPI_LINK_POSITIONS_KINEMATIC)
+        return fail(h, MPPI_ERR_INVALID, "obstacle avoidance is enabled: the link-position model stays MPPI_LINK_POSITIONS_KINEMATIC");
     h->link_positions = mode;
     return MPPI_OK;
 }
@@ -2468,6 +2618,64 @@ mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode)
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "simulated wrench: FrankaRidgeback handles only");
     *mode = h->simulated_wrench;
+    return MPPI_OK;
+}
+
+void mppi_default_obstacle_config(mppi_obstacle_config *out)
+{
+    if (!out) return;
+    out->limit = mppi_barrier{0.0, 1.0, 1e10};
+    out->radii[0] = 0.75;   // the objective's default self_collision_radii, then the end effector's
+    for (int i = 1; i < MPPI_OBSTACLE_POINTS; i++) out->radii[i] = 0.1;
+}
+
+mppi_status mppi_set_obstacle_avoidance(mppi_handle *h, const mppi_obstacle_config *config)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "obstacle avoidance: FrankaRidgeback handles only");
+    // the rollout launches' kernels are part of the launch plan and of a captured graph
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "obstacle avoidance is enabled before the first update");
+    if (h->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return fail(h, MPPI_ERR_INVALID, "obstacle avoidance needs the kinematic link-position model (mppi_set_link_positions)");
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    std::string why;
+    if (!check_obstacle_config(c, why)) return fail(h, MPPI_ERR_INVALID, why);
+    h->ob_config = c;
+    h->obstacle_avoidance = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_obstacle_avoidance(mppi_handle *h, int *enabled, mppi_obstacle_config *out)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->obstacle_avoidance ? 1 : 0;
+    if (h->obstacle_avoidance && out) *out = h->ob_config;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, int32_t count, double time)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
+    std::string why;
+    if (!check_obstacles(obstacles, count, time, why)) return fail(h, MPPI_ERR_INVALID, why);
+    for (int32_t o = 0; o < count; o++) h->ob_set[o] = obstacles[o];
+    h->ob_count = count;
+    h->ob_time = time;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *count, double *time)
+{
+    if (!h || !count) return MPPI_ERR_INVALID;
+    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
+    *count = h->ob_count;
+    if (time) *time = h->ob_time;
+    if (out16)
+        for (int32_t o = 0; o < h->ob_count; o++) out16[o] = h->ob_set[o];
     return MPPI_OK;
 }
 
@@ -2747,6 +2955,24 @@ mppi_status mppi_optimal_terms(mppi_handle *h, double *terms7)
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     std::memcpy(terms7, h->h_opt + 1, 7 * sizeof(double));
+    return MPPI_OK;
+}
+
+mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
+{
+    if (!h || !cost) return MPPI_ERR_INVALID;
+    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "obstacle cost: obstacle avoidance is not enabled");
+    HIP_TRY(hipSetDevice(h->device));
+    *cost = 0.0;
+    if (!h->published_once) return MPPI_OK;   // no filter() row yet
+    mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
+    if (st != MPPI_OK) return st;
+    // (the row's own update's table: behind opt_steps)
+    HIP_TRY(launch_fr_obstacle_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
+                                     h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    HIP_TRY(hipStreamSynchronize(h->stream_opt));
+    *cost = h->h_opt[1];
     return MPPI_OK;
 }
 

@@ -89,6 +89,28 @@ struct StepConst {
     int pad;
 };
 
+// The obstacle set of one update (mppi_set_obstacle_avoidance, mppi_set_obstacles): the avoidance
+// configuration, the update's time t0 and the set's reference time, and up to OB_MAX obstacles.
+// Each update writes its own behind its step constants and wrench rows (steps + 2 H:
+// launch_obstacle_table), so the filter() row reads the set and the time of the update it belongs
+// to and a replayed graph needs no node for it.  OB_POINTS: the eight sphere links, then the end effector.
+constexpr int OB_MAX = 16, OB_POINTS = 9;
+constexpr int OB_SPHERE = 0, OB_HALF_SPACE = 1;
+struct DevObstacle {
+    double position[3], velocity[3], normal[3], radius;
+    int kind;
+    unsigned mask;
+};
+struct ObstacleTable {
+    DevBarrier limit;
+    double radii[OB_POINTS];
+    double t0, t_ref;
+    int count, pad;
+    DevObstacle ob[OB_MAX];
+};
+// the table's room behind the 2 H step-constant slots, in StepConst units
+constexpr int OB_TABLE_STEPS = (int)((sizeof(ObstacleTable) + sizeof(StepConst) - 1) / sizeof(StepConst));
+
 // Quadratic point-mass plugin.
 struct DevPointMass {
     double inv_mass;

@@ -58,12 +58,22 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
-// This text is compiled as four translation units: by itself (the default mode's kernels
+// This text is compiled as six translation units: by itself (the default mode's kernels
 // and everything the host calls), and included by fr_coop_lp.hip (FR_COOP_LP_UNIT: the kinematic
 // link-position objective), fr_coop_wr.hip (FR_COOP_WR_UNIT: the simulated end-effector wrench in
-// the step) and fr_coop_wr_lp.hip (both).  A variant unit holds its kernels and their launchers only.
+// the step), fr_coop_wr_lp.hip (both), and fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip (FR_COOP_OB_UNIT
+// on top of LP: the obstacle term in the objective).  A variant unit holds its kernels and their
+// launchers only.
 #if defined(FR_COOP_LP_UNIT) || defined(FR_COOP_WR_UNIT)
 #define FR_COOP_VARIANT_UNIT 1
+#endif
+#if defined(FR_COOP_OB_UNIT) && !defined(FR_COOP_LP_UNIT)
+#error "the obstacle units are link-position units"
+#endif
+#ifdef FR_COOP_OB_UNIT
+#define FR_UNIT_OB true
+#else
+#define FR_UNIT_OB false
 #endif
 
 #ifdef PHASE_MARKS
@@ -1705,7 +1715,11 @@ __device__ __forceinline__ void launch_row_cost(const FrRolloutArgs &a, int64_t 
     if (!(lr < a.count || frow)) return;
     if (frow && (a.status->all_nan || a.status->sg_error)) return;   // no filter() when the update threw
     double J;
-    if constexpr (LP)
+    if constexpr (LP && FR_UNIT_OB)   // (the row's table: behind the step constants it reads)
+        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true, true>(*a.cost, frow ? a.fsteps : a.steps,
+                                                                 frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H,
+                                                                 lane, Lmodel + T_LO, mppi_cost::LinkModel{a.model, a.dt});
+    else if constexpr (LP)
         J = mppi_cost::rollout_cost<CK, EN, MB, KC, true>(*a.cost, frow ? a.fsteps : a.steps,
                                                            frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H, lane,
                                                            Lmodel + T_LO, mppi_cost::LinkModel{a.model, a.dt});
@@ -2010,7 +2024,16 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
     const ChunkLane L = chunk_lane(a, g, c, lane);
     PMARK(8);
     double cs;
-    if constexpr (LP)
+    if constexpr (LP && FR_UNIT_OB) {
+        // the relay group's chunks hold the folded filter() row beside this update's rows: that row's
+        // lanes read the previous update's table (ObstacleRef: a second pass, in such a wave only)
+        const bool frow = a.fcost != nullptr && group_row0(a, g) + (lane >> 4) == a.count;
+        const bool anyf = __builtin_amdgcn_ballot_w64(frow) != 0;
+        const mppi_cost::ObstacleRef ob{mppi_cost::obstacle_table_of(a.steps, a.H),
+                                        anyf ? mppi_cost::obstacle_table_of(a.fsteps, a.H) : nullptr, frow, L.kk};
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
+                                                                           mppi_cost::LinkModel{a.model, a.dt}, L.kk == 0, ob);
+    } else if constexpr (LP)
         cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
                                                                      mppi_cost::LinkModel{a.model, a.dt}, L.kk == 0);
     else
@@ -2291,7 +2314,19 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // are the same functions, by name and by instruction.
 // WR: the simulated end-effector wrench in the step (FrRolloutArgs::simulated_wrench, coop_rows),
 // again kernels and units of their own (fr_coop_wr.hip; with LP, fr_coop_wr_lp.hip).
-#if defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
+// OB: the obstacle term in the LP objective (FrRolloutArgs::link_positions == 2), units
+// fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip.
+#if defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_COOP_K fr_coop_wr_lp_ob_kernel
+#define FR_COOP_XK fr_coop_x_wr_lp_ob_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR true
+#elif defined(FR_COOP_OB_UNIT)
+#define FR_COOP_K fr_coop_lp_ob_kernel
+#define FR_COOP_XK fr_coop_x_lp_ob_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR false
+#elif defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
 #define FR_COOP_K fr_coop_wr_lp_kernel
 #define FR_COOP_XK fr_coop_x_wr_lp_kernel
 #define FR_UNIT_LP true
@@ -2348,7 +2383,8 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
     return at.sharedSizeBytes >= want ? 0u : (unsigned)(want - at.sharedSizeBytes);
 }
 
-// The variant units' launches (fr_coop_lp.hip, fr_coop_wr.hip, fr_coop_wr_lp.hip): the x kernel, and
+// The variant units' launches (fr_coop_lp.hip, fr_coop_wr.hip, fr_coop_wr_lp.hip and the two obstacle
+// units): the x kernel, and
 // the unit's fr_coop_*_kernel with wpb waves per workgroup and compact or 768-B records
 #define FR_UNIT_DECL(tag)                                                                                     \
     void launch_fr_coop_##tag##_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);                        \
@@ -2357,6 +2393,8 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
 FR_UNIT_DECL(lp)
 FR_UNIT_DECL(wr)
 FR_UNIT_DECL(wr_lp)
+FR_UNIT_DECL(lp_ob)
+FR_UNIT_DECL(wr_lp_ob)
 #undef FR_UNIT_DECL
 
 template <int CK, bool EN, int WPB, bool KC>
@@ -2377,6 +2415,8 @@ template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_OBSTACLES)
+        return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_ob_one(a, nb, s, WPB, KC);
     if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_one(a, nb, s, WPB, KC) : launch_fr_coop_wr_one(a, nb, s, WPB, KC);
     if (a.link_positions) return launch_fr_coop_lp_one(a, nb, s, WPB, KC);
 #endif
@@ -2388,6 +2428,7 @@ static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_OBSTACLES) return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_x(a, nb, s) : launch_fr_coop_lp_ob_x(a, nb, s);
     if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_x(a, nb, s) : launch_fr_coop_wr_x(a, nb, s);
     if (a.link_positions) return launch_fr_coop_lp_x(a, nb, s);
 #endif
@@ -2397,7 +2438,11 @@ static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 }
 
 #ifdef FR_COOP_VARIANT_UNIT
-#if defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
+#if defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_UNIT_FN(pre, post) pre##wr_lp_ob##post
+#elif defined(FR_COOP_OB_UNIT)
+#define FR_UNIT_FN(pre, post) pre##lp_ob##post
+#elif defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
 #define FR_UNIT_FN(pre, post) pre##wr_lp##post
 #elif defined(FR_COOP_WR_UNIT)
 #define FR_UNIT_FN(pre, post) pre##wr##post
@@ -2449,7 +2494,8 @@ bool fr_coop_is_update_kernel(const void *f)
     return f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, false> ||
            f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
            f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f) ||
-           fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f);
+           fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f) || fr_coop_lp_ob_is_update_kernel(f) ||
+           fr_coop_wr_lp_ob_is_update_kernel(f);
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at

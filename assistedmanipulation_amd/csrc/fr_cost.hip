@@ -41,7 +41,7 @@ using namespace mppi_cost;
 template <int CK, bool EN, bool KC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void fr_step_cost_kernel(FrCostArgs a)
 {
-    constexpr bool LP = false;
+    constexpr bool LP = false, OB = false;
 #include "fr_step_cost_kernel_body.inc"
 }
 // Two waves per SIMD here: the link positions and the pose are live beside the barrier chains, and
@@ -50,8 +50,45 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 template <int CK, bool EN, bool KC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_lp_kernel(FrCostArgs a)
 {
-    constexpr bool LP = true;
+    constexpr bool LP = true, OB = false;
 #include "fr_step_cost_kernel_body.inc"
+}
+// The same with the obstacle term (FrCostArgs::link_positions == FR_LINKS_OBSTACLES)
+template <int CK, bool EN, bool KC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_ob_kernel(FrCostArgs a)
+{
+    constexpr bool LP = true, OB = true;
+#include "fr_step_cost_kernel_body.inc"
+}
+
+// An update's obstacle table from the launch's arguments into its place behind the step constants
+__global__ __launch_bounds__(64) void obstacle_table_kernel(ObstacleTable t, ObstacleTable *out)
+{
+    static_assert(sizeof(ObstacleTable) % sizeof(double) == 0, "copied as doubles");
+    const double *src = reinterpret_cast<const double *>(&t);
+    double *dst = reinterpret_cast<double *>(out);
+    for (int i = threadIdx.x; i < (int)(sizeof(ObstacleTable) / sizeof(double)); i += 64) dst[i] = src[i];
+}
+
+// The obstacle term of the filter() row summed over its steps in step order, undiscounted, as
+// fr_terms_kernel sums the reference's seven (one wave, lane = step)
+__global__ __launch_bounds__(64) void fr_obstacle_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
+                                                               const DevModel *model, double dt, double *out1)
+{
+    const int lane = threadIdx.x;
+    const ObstacleTableK T = obstacle_table_of(steps, H);
+    double tot = 0.0;
+    for (int base = 0; base < H; base += 64) {
+        const int n = (H - base < 64) ? H - base : 64;
+        const int k = base + (lane < n ? lane : 0);
+        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);   // (q, qd) pairs and the EE position: both layouts
+        double qj[10], lp[SC_LINKS][3];
+        for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
+        link_fk(*model, qj, lp);
+        const double t = obstacle_term(T, lp, r + REC_EE, dt, k);
+        for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
+    }
+    if (lane == 0) *out1 = tot;
 }
 
 // The optimal rollout's per-term totals (AssistedManipulation's accumulators after filter(),
@@ -100,13 +137,37 @@ hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const do
     return hipGetLastError();
 }
 
+hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(obstacle_table_kernel, dim3(1), dim3(64), 0, s, t, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                    double dt, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_obstacle_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    return hipGetLastError();
+}
+
 hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s)
 {
     const int64_t rows = a.count + (a.fcost ? 1 : 0);
     if (rows == 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(64);
     // the records' layout is the launch's that wrote them (FrCostArgs::compact)
-    if (a.link_positions) {
+    if (a.link_positions == FR_LINKS_OBSTACLES) {
+        if (!a.model) return hipErrorInvalidValue;
+        if (a.compact) {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
+        } else {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
+        }
+    } else if (a.link_positions) {
         if (!a.model) return hipErrorInvalidValue;
         if (a.compact) {
             if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);

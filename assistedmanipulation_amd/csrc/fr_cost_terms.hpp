@@ -155,6 +155,90 @@ struct LinkModel {
     double dt;
 };
 
+// ---- environment obstacles (mppi_set_obstacle_avoidance, mppi_set_obstacles) --------------------
+// The step's obstacle term: sum over the table's obstacles o, in order, and over the robot's points
+// i of mask_o, in order, of Left(limit)(clearance).  The points are the eight sphere links lp[0..7]
+// (link_fk: lagged like the self-collision term's) and the record's grasp-frame position ee; obstacle
+// o sits at position + velocity tau_k, tau_k = (t0 + k dt) - t_ref.  A sphere's clearance is
+// |p - c| - (radii[i] + radius); a half-space's n . (p - c) - radii[i], no square root.  k and the
+// points are the lane's; the table and o are the wave's: a runtime loop over count, and through an
+// ObstacleTableK pointer (the rollouts) every table read is a scalar load.  The products and sums
+// of tau_k and c are rounded one by one, as the host reference writes them.
+// TP: const ObstacleTable * (the device object: its table is a kernel argument) or ObstacleTableK.
+template <typename TP>
+__device__ __forceinline__ double obstacle_term(TP T, const double (*lp)[3], const double *ee, double dt, int k)
+{
+    const double tau = __dsub_rn(__dadd_rn(T->t0, __dmul_rn((double)k, dt)), T->t_ref);
+    const int count = T->count;
+    const int n = count < OB_MAX ? count : OB_MAX;   // (never past the table, whatever it holds)
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    double term = 0.0;
+#pragma unroll 1
+    for (int o = 0; o < n; o++) {
+        const double c0 = __dadd_rn(T->ob[o].position[0], __dmul_rn(T->ob[o].velocity[0], tau));
+        const double c1 = __dadd_rn(T->ob[o].position[1], __dmul_rn(T->ob[o].velocity[1], tau));
+        const double c2 = __dadd_rn(T->ob[o].position[2], __dmul_rn(T->ob[o].velocity[2], tau));
+        const unsigned mask = T->ob[o].mask;
+        if (T->ob[o].kind == OB_HALF_SPACE) {
+            const double n0 = T->ob[o].normal[0], n1 = T->ob[o].normal[1], n2 = T->ob[o].normal[2];
+#pragma unroll
+            for (int i = 0; i < OB_POINTS; i++) {
+                const double *p = i < SC_LINKS ? lp[i] : ee;
+                const double v = ((n0 * (p[0] - c0) + n1 * (p[1] - c1)) + n2 * (p[2] - c2)) - T->radii[i];
+                const double b = left_barrier(bound, scale, mx, v);
+                term += ((mask >> i) & 1u) ? b : 0.0;
+            }
+        } else {
+            const double ro = T->ob[o].radius;
+#pragma unroll
+            for (int i = 0; i < OB_POINTS; i++) {
+                const double *p = i < SC_LINKS ? lp[i] : ee;
+                const double d0 = p[0] - c0, d1 = p[1] - c1, d2 = p[2] - c2;
+                const double v = sqrt((d0 * d0 + d1 * d1) + d2 * d2) - (T->radii[i] + ro);
+                const double b = left_barrier(bound, scale, mx, v);
+                term += ((mask >> i) & 1u) ? b : 0.0;
+            }
+        }
+    }
+    return term;
+}
+
+// An update's obstacle table as the rollouts' objective reads it: nothing writes it during a launch
+// (obstacle_table_kernel ran before), so it is addressed in the constant address space, and its
+// address is made the wave's by v_readfirstlane - it is the same on every lane, but where it hangs
+// on the wave's row (the folded filter() row reads fsteps) the compiler cannot see that.  Uniform
+// address and constant space together make every read of the table an s_load.
+typedef const __attribute__((address_space(4))) ObstacleTable *ObstacleTableK;
+__device__ __forceinline__ ObstacleTableK obstacle_table_of(const StepConst *steps, int H)
+{
+    const uint64_t a = reinterpret_cast<uint64_t>(steps + 2 * (int64_t)H);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return (ObstacleTableK)(((uint64_t)hi << 32) | lo);
+}
+
+// Where a lane's step finds its obstacles: the table behind its update's step constants and wrench
+// rows (obstacle_table_of) and its step index k.  A wave of the x kernel's objective may hold rows
+// of this update beside the folded filter() row, which reads the previous update's table: such a
+// wave passes that table as ftab (else null) and frow on the row's lanes, and the term runs once
+// per table, both times on scalar loads.
+struct ObstacleRef {
+    ObstacleTableK tab, ftab;
+    bool frow;
+    int k;
+};
+__device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt)
+{
+    double term = 0.0;
+    const int np = ob.ftab ? 2 : 1;
+#pragma unroll 1
+    for (int pass = 0; pass < np; pass++) {
+        const ObstacleTableK T = pass ? ob.ftab : ob.tab;
+        const double t = obstacle_term(T, lp, ee, dt, ob.k);
+        term = (pass == 0 || ob.frow) ? t : term;
+    }
+    return term;
+}
+
 // Per-joint parameters of the objective in LDS, joint j at Lj[j JS ..]: lower barrier (bound,
 // scale, max), upper barrier, velocity weight - uniform loads next to their use instead of 84
 // scalar registers the compiler loaded up front and spilled.  fr_cost.hip stages them with stride
@@ -237,11 +321,14 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 // J v and J_a J_a^T stored; else the 768-B record, whose motion subspaces they are formed from)
 // LP: the kinematic link-position model - the self-collision term from the record's link positions
 // (lm, first: record_self_collision) instead of the zero stub's constant
-template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false>
+// OB (with LP): the obstacle term on the same link positions (ob: obstacle_cost), added after the
+// reference's terms; the link FK then runs whether or not the self-collision switch is on
+template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
                                                              const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
-                                                             bool first = false)
+                                                             bool first = false, ObstacleRef ob = ObstacleRef{})
 {
+    static_assert(LP || !OB, "the obstacles read the kinematic link positions");
     double j0 = 0.0, j1 = 0.0, v0 = 0.0, v1 = 0.0;
     int off = 0;
     // JG joints at a time: their parameters are read after the previous group's terms (left to
@@ -322,6 +409,41 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
         const double yc = (Cs.yaw_c + Cs.yaw_l * fabs(ay)) + Cs.yaw_q * ay * ay;
         wc += isnan(yaw) ? 0.0 : yc;
         wc += left_barrier(Cs.ws_above, ee[2] - rb2);
+    }
+    if constexpr (OB) {
+        // One link FK for the self-collision and the obstacle terms, after every other term: the
+        // 24 link coordinates then live beside six finished terms and the end-effector position
+        // instead of beside the record's tail and the kinematic sums.  The terms are added in
+        // get_cost's order all the same.
+        double t_joint = Cs.en_joint ? joint : 0.0, t_work = Cs.en_work ? wc : 0.0, t_energy = 0.0;
+        if constexpr (EN) {   // energy_cost (:211-222)
+            const double E = r[REC_E];
+            t_energy = left_barrier(Cs.en_below, E) + right_barrier(Cs.en_above, E);
+        }
+        double t_vel = Cs.en_vel ? vel : 0.0;
+        double t_traj = Cs.en_traj ? trajectory_term(Cs, sc, vl) : 0.0;
+        double t_manip = Cs.en_manip ? manipulability_term(Cs, jj) : 0.0;
+        double pe[3] = {ee[0], ee[1], ee[2]};
+        int dep2 = 0;   // the (q, qd) reloads wait for those terms (an index, as above)
+        asm volatile("" : "+v"(dep2), "+v"(pe[0]), "+v"(pe[1]), "+v"(pe[2]) : "v"(t_joint), "v"(t_work), "v"(t_energy), "v"(t_vel), "v"(t_traj), "v"(t_manip));
+        const double *pq = reinterpret_cast<const double *>(tp + dep2);
+        double qj[10], lp[SC_LINKS][3];
+#pragma unroll
+        for (int j = 0; j < 10; j++) qj[j] = lagged_q(pq[2 * j], pq[2 * j + 1], lm.dt, first);
+        link_fk(*lm.model, qj, lp);
+        double sct = 0.0;
+        if (Cs.en_self) sct = self_collision_term<false>(Cs, lp);
+        const double obt = obstacle_cost(ob, lp, pe, lm.dt);
+        double cost = 0.0;
+        cost += t_joint;
+        cost += sct;
+        cost += t_work;
+        if constexpr (EN) cost += t_energy;
+        cost += t_vel;
+        cost += t_traj;
+        cost += t_manip;
+        cost += obt;
+        return cost;
     }
     double cost = 0.0;
     cost += Cs.en_joint ? joint : 0.0;
@@ -445,34 +567,39 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
 
 // gamma_k times the objective at step record r (AssistedManipulation: r holds the record's (q, qd)
 // pairs, the rest is read from the stored record src; TrackPoint: r holds the record up to REC_VL)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
 __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &sc, const double *r, const double *Lj,
-                                           const double2 *src, LinkModel lm = LinkModel{}, bool first = false)
+                                           const double2 *src, LinkModel lm = LinkModel{}, bool first = false,
+                                           ObstacleRef ob = ObstacleRef{})
 {
     if constexpr (CK == CK_TRACK_POINT) {
         if constexpr (LP) {
             double lp[SC_LINKS][3];
-            if (Cs.tp_en_self) {
+            if (Cs.tp_en_self || OB) {
                 double qj[10];
 #pragma unroll
                 for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], lm.dt, first);
                 link_fk(*lm.model, qj, lp);
             }
-            return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
+            if constexpr (OB)
+                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost(ob, lp, r + REC_EE, lm.dt));
+            else
+                return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
         } else {
             return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4]);
         }
     } else {
-        if constexpr (LP) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
+        if constexpr (OB) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true, true>(Cs, sc, r, Lj, src, lm, first, ob);
+        else if constexpr (LP) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
         else return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG>(Cs, sc, r, Lj, src);
     }
 }
 
 // gamma_k times the objective at the stored step record rk (FR_REC doubles, or FR_REC_C with KC;
 // 16-byte aligned)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
 __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const StepConst &sc, const double *rk, const double *Lj,
-                                                  LinkModel lm = LinkModel{}, bool first = false)
+                                                  LinkModel lm = LinkModel{}, bool first = false, ObstacleRef ob = ObstacleRef{})
 {
     double r[FR_NREC];
     const double2 *src = reinterpret_cast<const double2 *>(rk);
@@ -483,7 +610,8 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
         r[2 * i] = v.x;
         r[2 * i + 1] = v.y;
     }
-    if constexpr (LP) return step_cost<CK, EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
+    if constexpr (OB) return step_cost<CK, EN, JS, KC, JG, true, true>(Cs, sc, r, Lj, src, lm, first, ob);
+    else if constexpr (LP) return step_cost<CK, EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
     else return step_cost<CK, EN, JS, KC, JG>(Cs, sc, r, Lj, src);
 }
 
@@ -492,7 +620,8 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
 // lane k evaluates step k (64 steps a pass) and the wave sums the step costs in step order, as the
 // reference accumulates J += cost (mppi.cpp:322-337); a NaN step makes the sum NaN (the reference's
 // early stop), canonicalised to the quiet NaN it stores.  The same value on every lane.
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, bool LP = false>
+// OB: the obstacle term from the table behind stp (one row a wave: one table)
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, bool LP = false, bool OB = false>
 __device__ __forceinline__ double rollout_cost(const DevCost &Cs, const StepConst *stp, const double *rec, int H, int lane,
                                                const double *Lj, LinkModel lm = LinkModel{})
 {
@@ -502,7 +631,10 @@ __device__ __forceinline__ double rollout_cost(const DevCost &Cs, const StepCons
         const int n = (H - base < 64) ? H - base : 64;
         const int k = base + (lane < n ? lane : 0);
         double c;
-        if constexpr (LP) c = record_step_cost<CK, EN, JS, KC, 1, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0);
+        if constexpr (OB)
+            c = record_step_cost<CK, EN, JS, KC, 1, true, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0,
+                                                                ObstacleRef{obstacle_table_of(stp, H), nullptr, false, k});
+        else if constexpr (LP) c = record_step_cost<CK, EN, JS, KC, 1, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0);
         else c = record_step_cost<CK, EN, JS, KC>(Cs, stp[k], rec + (int64_t)k * RS, Lj);
         // J += c_i in step order; the lane reads eight at a time, ahead of their adds
         int i = 0;

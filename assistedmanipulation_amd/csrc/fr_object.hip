@@ -444,7 +444,22 @@ __global__ __launch_bounds__(64) void fr_object_kernel(ObjArgs a)
     }
 }
 
+// mppi_dynamics_obstacle_cost: the obstacle term (fr_cost_terms.hpp obstacle_term) at the positions
+// the object cached at its last calculate() - the sphere links PIVOT .. PANDA_LINK7 and the grasp
+// frame - with the table's own time (step 0: tau = t0 - t_ref)
+__global__ __launch_bounds__(64) void fr_object_obstacle_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
+{
+    if (threadIdx.x != 0) return;
+    *out1 = mppi_cost::obstacle_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, 0.0, 0);
+}
+
 namespace mppi_eng {
+
+hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_object_obstacle_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
+    return hipGetLastError();
+}
 
 hipError_t launch_fr_object(const ObjArgs &a, hipStream_t s)
 {

@@ -1,5 +1,6 @@
 // fr_step_cost_kernel_body.inc - the body of fr_step_cost_kernel and fr_step_cost_lp_kernel
-// (fr_cost.hip); LP (a constexpr bool of the including kernel): the kinematic link-position model.
+// (fr_cost.hip); LP (a constexpr bool of the including kernel): the kinematic link-position model;
+// OB (likewise, with LP): the obstacle term (fr_step_cost_ob_kernel).
     __shared__ double Lj[FR_NB * JT_STRIDE];
     const int lane = threadIdx.x;
     const int64_t row = blockIdx.x;
@@ -16,7 +17,7 @@
             Lj[i] = *src;
         }
     __syncthreads();
-    const double J = rollout_cost<CK, EN, JT_STRIDE, KC, LP>(Cs, stp, frow ? a.frec : a.rec + row * H * (KC ? FR_REC_C : FR_REC), H,
+    const double J = rollout_cost<CK, EN, JT_STRIDE, KC, LP, OB>(Cs, stp, frow ? a.frec : a.rec + row * H * (KC ? FR_REC_C : FR_REC), H,
                                                              lane, Lj, LinkModel{a.model, a.dt});
     if (lane != 0) return;
     if (frow) *a.fcost = J;

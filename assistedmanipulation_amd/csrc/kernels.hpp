@@ -123,6 +123,8 @@ struct FinishArgs {
 // large as a StepConst), so that whatever reads an update's step constants finds its wrench rows.
 constexpr int FR_WRENCH_ROW = 8;
 static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows behind the step constants");
+// FrRolloutArgs / FrCostArgs::link_positions
+constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2;
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -168,6 +170,8 @@ struct FrRolloutArgs {
     // the self-collision term on each record's link positions (fr_coop.hip's *_lp_kernel; read by
     // the host's launch selection only).  In the padding behind costs_in_launch: the argument
     // block's size and every other offset stay what the default mode's kernels were built for.
+    // FR_LINKS_OBSTACLES: the model with the obstacle term as well (mppi_set_obstacle_avoidance; the
+    // *_ob_kernel units), its table behind the step constants and wrench rows (steps + 2 H, fsteps + 2 H).
     int link_positions;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
@@ -257,6 +261,7 @@ struct FrCostArgs {
     CostStats *stats;         // the update's rollout costs (not filter()'s) folded in, or null
     // the kinematic link-position model (mppi_set_link_positions): the self-collision term from the
     // records' link positions, which the objective rebuilds with the model and the rollout's dt
+    // (FR_LINKS_OBSTACLES: with the obstacle term from the table at steps + 2 H, fsteps + 2 H)
     int link_positions;
     const DevModel *model;
     double dt;
@@ -476,6 +481,15 @@ hipError_t launch_pm_update(const PmFusedArgs &a, hipStream_t s);
 // link_model: the kinematic link-position model's (else null: the zero stub's constant), dt the rollouts'
 hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const double *rec, int H, bool compact, double *out7,
                            hipStream_t s, const DevModel *link_model = nullptr, double dt = 0.0);
+// An update's obstacle table, by value into out (behind the update's step constants, engine_types.hpp)
+hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hipStream_t s);
+// The obstacle term of one rollout's H records summed over its steps in step order, undiscounted
+// (next to launch_fr_terms' seven totals), from the table behind `steps`
+hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                    double dt, double *out1, hipStream_t s);
+// mppi_dynamics_obstacle_cost: the term at the object's cached link and end-effector positions,
+// tau = t.t0 - t.t_ref
+hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
 
 
 }  // namespace mppi_eng

@@ -175,6 +175,18 @@ class PinocchioDynamicsObject:
     def get_link_position(self, link):
         return self.link_positions()[int(link)]
 
+    def obstacle_cost(self, config, obstacles, elapsed):
+        """mppi_dynamics_obstacle_cost: the obstacle term (Trajectory.set_obstacle_avoidance) of
+        `obstacles` moved by `elapsed` seconds, at the link and end-effector positions the object
+        cached at its last call.  `config`: an ObstacleAvoidance or None (the defaults).  The object
+        must be in the kinematic link-position model."""
+        from .obstacles import ObstacleAvoidance, obstacles_to_c
+        c = (config or ObstacleAvoidance()).to_c()
+        arr, n = obstacles_to_c(obstacles)
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_dynamics_obstacle_cost(self._h, C.byref(c), arr, n, float(elapsed), C.byref(v)))
+        return v.value
+
     def query_row(self):
         """The members after the last call as MPPI_DYNAMICS_QUERY_N doubles."""
         o = np.zeros(abi.MPPI_DYNAMICS_QUERY_N)

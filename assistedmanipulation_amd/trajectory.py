@@ -18,6 +18,7 @@ import numpy as np
 
 from . import abi
 from ._lib import load
+from .obstacles import ObstacleAvoidance, obstacle_from_c, obstacles_to_c
 from .config import Configuration
 
 
@@ -315,6 +316,41 @@ class Trajectory:
             return abi.MPPI_SIMULATED_WRENCH_OFF
         self._check(st)
         return m.value
+
+    def set_obstacle_avoidance(self, config=None):
+        """mppi_set_obstacle_avoidance: sphere and half-space obstacles in the rollouts' objective,
+        with `config` (an ObstacleAvoidance; None: the defaults).  FrankaRidgeback handles in the
+        kinematic link-position model, before the first update; fixed for the handle's life."""
+        c = (config or ObstacleAvoidance()).to_c()
+        self._check(self._L.mppi_set_obstacle_avoidance(self._h, C.byref(c)))
+
+    @property
+    def obstacle_avoidance(self):
+        """The ObstacleAvoidance configuration the handle runs with, or None when it is off."""
+        on, c = C.c_int(0), abi.mppi_obstacle_config()
+        self._check(self._L.mppi_get_obstacle_avoidance(self._h, C.byref(on), C.byref(c)))
+        return ObstacleAvoidance.from_c(c) if on.value else None
+
+    def set_obstacles(self, obstacles, time):
+        """mppi_set_obstacles: replace the whole set (SphereObstacle / HalfSpaceObstacle, at most 16;
+        an empty list clears it), given at reference time `time`.  Between any two updates; every
+        rank of a sharded run sets the same one."""
+        arr, n = obstacles_to_c(obstacles)
+        self._check(self._L.mppi_set_obstacles(self._h, arr, n, float(time)))
+
+    def obstacles(self):
+        """(the current set as a list, its reference time) (mppi_get_obstacles)."""
+        arr = (abi.mppi_obstacle * abi.MPPI_MAX_OBSTACLES)()
+        n, t = C.c_int32(0), C.c_double(0.0)
+        self._check(self._L.mppi_get_obstacles(self._h, arr, C.byref(n), C.byref(t)))
+        return [obstacle_from_c(arr[i]) for i in range(n.value)], t.value
+
+    def get_optimal_obstacle_cost(self):
+        """mppi_optimal_obstacle_cost: the obstacle term of the last update's filter() row summed over
+        its steps, undiscounted, next to get_optimal_terms' seven totals."""
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_optimal_obstacle_cost(self._h, C.byref(v)))
+        return v.value
 
     def set_noise_source(self, source, seed=0x5EED):
         self._check(self._L.mppi_set_noise_source(self._h, int(source), int(seed)))

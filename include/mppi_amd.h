@@ -399,6 +399,66 @@ mppi_status mppi_get_link_positions(mppi_handle *h, int *mode);
 mppi_status mppi_set_simulated_wrench(mppi_handle *h, int mode);
 mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode);
 
+/* Obstacle avoidance: sphere and half-space obstacles in the rollouts' objective.  Nothing in the
+ * reference computes this; it is this build's own addition, opt-in and off by default.
+ * An obstacle set is at most MPPI_MAX_OBSTACLES obstacles with a reference time t_ref.  At the cost
+ * of step k of an update at time t0 the elapsed time is tau_k = (t0 + k dt) - t_ref (the time
+ * get_cost is called with, mppi.cpp:322-337, less t_ref) and obstacle o sits at
+ * c_o(k) = position + velocity tau_k.  SPHERE: centre c_o(k), radius >= 0.  HALF_SPACE: the solid
+ * {x : n . (x - c_o(k)) <= 0}, n a unit normal pointing into free space (radius ignored).
+ * The robot is MPPI_OBSTACLE_POINTS spheres: points 0..7 are get_link_position(MPPI_LINK_PIVOT + i)
+ * of the kinematic link-position model, lagged exactly as the self-collision term sees them (q_0
+ * for k = 0, q_{k-1} after); point 8 is the end-effector (grasp-frame) position the objective
+ * reads, with the same lag.  Their radii are the configuration's radii[]; the defaults are the
+ * objective's default self-collision radii (0.75, then 0.1 x 7) and 0.1 for the end effector.
+ * Point i is tested against obstacle o only if bit i of the obstacle's mask is set (a floor plane
+ * leaves out the base sphere, which sits at z = 0 with radius 0.75).  Clearance:
+ *   sphere      v = |p_i - c_o(k)| - (radii[i] + radius_o)
+ *   half-space  v = n_o . (p_i - c_o(k)) - radii[i]
+ * and the step's term is sum_o sum_{i in mask_o} Left(limit)(v), the reference's
+ * LeftInverseBarrierFunction (cost.hpp:74-99; default limit {0, 1, 1e10}), obstacles and points in
+ * index order.  It is added to the objective's get_cost of the step, before the discount, for
+ * AssistedManipulation and TrackPoint, with or without the energy tank, in the rollouts and in
+ * filter()'s optimal rollout; a NaN term makes the rollout NaN like any step cost.
+ * mppi_set_obstacle_avoidance (config NULL: the defaults) selects the obstacle kernels for the
+ * handle's life: FrankaRidgeback handles only (MPPI_ERR_UNSUPPORTED otherwise), before the first
+ * update and with the handle in MPPI_LINK_POSITIONS_KINEMATIC (MPPI_ERR_INVALID otherwise, the
+ * message says which; the link-position model is fixed from then on); the configuration's values
+ * must be finite and its radii >= 0.  mppi_get_obstacle_avoidance: enabled = 0 for a handle that
+ * never enabled it (out is then untouched).
+ * mppi_set_obstacles replaces the whole set between any two updates, like mppi_set_forecast
+ * (count = 0 clears it); the set and its time reach every later update, captured graphs included.
+ * MPPI_ERR_INVALID when avoidance is not enabled, count is outside [0, MPPI_MAX_OBSTACLES], a kind
+ * is unknown, a mask has bits above bit 8, a value is not finite, a radius is negative, or a
+ * half-space normal is off unit length (| |n| - 1 | > 1e-9).  Not to be called concurrently with an
+ * update.  Sharded handles take the configuration and the set per handle: every rank must set the
+ * same ones.  mppi_get_obstacles: out16 has room for MPPI_MAX_OBSTACLES.
+ * mppi_optimal_obstacle_cost: the obstacle term of the last update's filter() row summed over its
+ * steps, undiscounted, next to mppi_optimal_terms' seven totals (which, like mppi_cost_evaluate,
+ * keep their terms and totals as they are); waits for (or runs) that filter() the same way; 0 with
+ * an empty set or before the first published update, MPPI_ERR_UNSUPPORTED when avoidance is off.
+ * Added after ABI version 5 without a version change (new structs only): detect by symbol. */
+#define MPPI_MAX_OBSTACLES 16
+#define MPPI_OBSTACLE_POINTS 9
+#define MPPI_OBSTACLE_SPHERE 0
+#define MPPI_OBSTACLE_HALF_SPACE 1
+#define MPPI_OBSTACLE_MASK_ALL 0x1FFu
+typedef struct mppi_obstacle {
+    int32_t kind;     /* MPPI_OBSTACLE_* */
+    uint32_t mask;    /* bit i: robot point i is tested */
+    double position[3], velocity[3], normal[3], radius;
+} mppi_obstacle;
+typedef struct mppi_obstacle_config {
+    mppi_barrier limit;                       /* left */
+    double radii[MPPI_OBSTACLE_POINTS];
+} mppi_obstacle_config;
+void mppi_default_obstacle_config(mppi_obstacle_config *out);
+mppi_status mppi_set_obstacle_avoidance(mppi_handle *h, const mppi_obstacle_config *config);
+mppi_status mppi_get_obstacle_avoidance(mppi_handle *h, int *enabled, mppi_obstacle_config *out);
+mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, int32_t count, double time);
+mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *count, double *time);
+mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost);
+
 /* Phase-split update for callers that run the collectives themselves (multi-GPU with an
  * external communicator, or two shards on one device in tests).  Between phase 1 and 2 the
  * caller all-reduces (sum) the R + 1 doubles of mppi_device_costs(h) - the R costs and slot R,
@@ -622,6 +682,12 @@ mppi_status mppi_cost_evaluate(const mppi_cost_desc *cost, mppi_dynamics *d, con
  * the zero mode. */
 mppi_status mppi_dynamics_set_link_positions(mppi_dynamics *d, int mode);
 mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out);
+/* The obstacle term of mppi_set_obstacle_avoidance (above) at the object's cached link positions
+ * and end-effector position after its last call, at tau = elapsed; stateless in the obstacles
+ * (config NULL: the defaults; the set is validated as mppi_set_obstacles validates it).
+ * MPPI_ERR_INVALID unless the object is in MPPI_LINK_POSITIONS_KINEMATIC. */
+mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
+                                        const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost);
 /* add_end_effector_simulated_wrench (6 doubles: force, moment; semantics above): cumulative; the
  * next mppi_dynamics_step applies the sum and zeroes it.  get_end_effector_simulated_wrench: the
  * wrench the last step applied, zeros before any step. */

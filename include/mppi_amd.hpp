@@ -245,6 +245,43 @@ public:
         int mode = MPPI_SIMULATED_WRENCH_OFF;
         return mppi_get_simulated_wrench(m_h, &mode) == MPPI_OK ? mode : MPPI_SIMULATED_WRENCH_OFF;
     }
+    // Obstacle avoidance (mppi_set_obstacle_avoidance; nullptr: the default configuration): sphere
+    // and half-space obstacles in the rollouts' objective.  A FrankaRidgeback trajectory in the
+    // kinematic link-position model, before the first update; false and a message on stderr otherwise.
+    bool set_obstacle_avoidance(const mppi_obstacle_config *config = nullptr)
+    {
+        if (mppi_set_obstacle_avoidance(m_h, config) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // whether it is on, and the configuration it runs with
+    bool obstacle_avoidance(mppi_obstacle_config *out = nullptr) const
+    {
+        int on = 0;
+        return mppi_get_obstacle_avoidance(m_h, &on, out) == MPPI_OK && on != 0;
+    }
+    // the whole set, given at reference time `time` (mppi_set_obstacles): between any two updates
+    bool set_obstacles(const std::vector<mppi_obstacle> &obstacles, double time)
+    {
+        if (mppi_set_obstacles(m_h, obstacles.data(), (int32_t)obstacles.size(), time) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    std::vector<mppi_obstacle> obstacles(double *time = nullptr) const
+    {
+        std::vector<mppi_obstacle> out(MPPI_MAX_OBSTACLES);
+        int32_t n = 0;
+        if (mppi_get_obstacles(m_h, out.data(), &n, time) != MPPI_OK) n = 0;
+        out.resize((size_t)n);
+        return out;
+    }
+    // the obstacle term of the optimal rollout, summed over its steps (mppi_optimal_obstacle_cost)
+    double get_optimal_obstacle_cost()
+    {
+        double c = 0.0;
+        if (mppi_optimal_obstacle_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
+        return c;
+    }
     Trajectory(const Trajectory &) = delete;
     Trajectory &operator=(const Trajectory &) = delete;
 
@@ -536,6 +573,14 @@ public:
         return {p[3 * l], p[3 * l + 1], p[3 * l + 2]};
     }
     int link_positions() const override { return m_configuration.link_positions ? MPPI_LINK_POSITIONS_KINEMATIC : -1; }
+    // the obstacle term of mppi_set_obstacle_avoidance at the positions cached by the last call, with
+    // the obstacles moved by `elapsed` seconds (mppi_dynamics_obstacle_cost; the kinematic model only)
+    double obstacle_cost(const std::vector<mppi_obstacle> &obstacles, double elapsed, const mppi_obstacle_config *config = nullptr)
+    {
+        double c = 0.0;
+        check(mppi_dynamics_obstacle_cost(object(), config, obstacles.data(), (int32_t)obstacles.size(), elapsed, &c));
+        return c;
+    }
     std::vector<double> get_joint_position() { return query(0, 12); }
     std::vector<double> get_joint_velocity() { return query(12, 12); }
     std::vector<double> get_joint_acceleration() { return query(24, 12); }
