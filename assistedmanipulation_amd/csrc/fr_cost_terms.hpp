@@ -24,29 +24,37 @@ constexpr int CK_ASSISTED_MANIPULATION = 1, CK_TRACK_POINT = 3;   // mppi_cost_k
 
 // x / d from v_rcp_f64 and one Newton correction applied to the product (four ops; the rcp's
 // 2.8e-8 relative error squares to ~1e-15, against the IEEE quotient's ten-op sequence).  Only
-// for barrier quotients: d = 0 (v on the bound) gives NaN, and there the barrier selects `over`.
+// for barrier quotients, whose distance d from the bound is kept at or above 2^-512.  Below about
+// 2^-1022 the rcp is inf and the product overflows, and the result was NaN (inf * 0, inf - inf)
+// where the barrier is 0 (x = 0: the fingers' scale-0 barriers) or its maximum cost; a bound of
+// exactly 0.0 and a joint one subnormal inside it get there.  The barriers' values do not change
+// for d >= 2^-512, and below it x / 2^-512 is what x / d is: 0 for x = 0, beyond any maximum cost
+// for x > 0.  d <= 0 and a NaN d become 2^-512 too: there the barriers select `over`.
 __device__ __forceinline__ double fquot(double x, double d)
 {
+    d = __builtin_fmax(d, 0x1p-512);
     const double r = __builtin_amdgcn_rcp(d);
     const double t = x * r;
     const double e = __builtin_fma(-d, r, 1.0);
     return __builtin_fma(t, e, t);
 }
 
-// AssistedManipulation barriers (assisted_manipulation.cpp), written as selects
+// AssistedManipulation barriers (assisted_manipulation.cpp), written as selects: `under` strictly
+// inside the bound, `over` on it, beyond it and for a NaN v (whose `over` is NaN, as the
+// reference's min(scale / NaN, max) is)
 __device__ __forceinline__ double right_barrier(double bound, double scale, double mx, double v)
 {
     const double d = v - bound;
     const double over = mx + scale * (d * d);
     const double under = smin(fquot(scale, bound - v), mx);
-    return (v >= bound) ? over : under;
+    return (v < bound) ? under : over;
 }
 __device__ __forceinline__ double left_barrier(double bound, double scale, double mx, double v)
 {
     const double d = bound - v;
     const double over = mx + scale * (d * d);
     const double under = smin(fquot(scale, v - bound), mx);
-    return (v <= bound) ? over : under;
+    return (v > bound) ? under : over;
 }
 __device__ __forceinline__ double right_barrier(const DevBarrier &b, double v) { return right_barrier(b.bound, b.scale, b.max, v); }
 __device__ __forceinline__ double left_barrier(const DevBarrier &b, double v) { return left_barrier(b.bound, b.scale, b.max, v); }
