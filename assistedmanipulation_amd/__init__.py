@@ -19,6 +19,7 @@ from .trajectory import (AssistedManipulation, Cost, Dynamics, EngineError, Trac
                          comm_unique_id, shard_range)
 
 from .obstacles import HalfSpaceObstacle, ObstacleAvoidance, SphereObstacle, obstacle_clearance  # noqa: E402
+from .safety import TrajectorySafetyFilter  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
 from .dynamics import DynamicsForecast, EndEffectorState, PinocchioDynamicsObject, evaluate_cost  # noqa: E402
 
@@ -29,5 +30,5 @@ __all__ = [
     "kalman_forecast_configuration", "AssistedManipulation", "TrackPoint", "Cost", "Dynamics",
     "EngineError", "FrankaRidgebackDynamics", "PointMassDynamics", "QuadraticCost", "Trajectory",
     "comm_unique_id", "shard_range", "Predicted", "ObstacleAvoidance", "SphereObstacle", "HalfSpaceObstacle",
-    "obstacle_clearance",
+    "obstacle_clearance", "TrajectorySafetyFilter",
 ]

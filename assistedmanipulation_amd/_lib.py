@@ -98,6 +98,12 @@ PROTOTYPES = {
     "mppi_dynamics_get_end_effector_simulated_wrench": (C.c_int, [_h, _dp]),
     "mppi_dynamics_set_simulated_wrench": (C.c_int, [_h, C.c_int]),
     "mppi_dynamics_get_simulated_wrench": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_default_safety_filter": (None, [C.POINTER(abi.mppi_safety_filter_desc)]),
+    "mppi_set_safety_filter": (C.c_int, [_h, C.POINTER(abi.mppi_safety_filter_desc)]),
+    "mppi_get_safety_filter": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_safety_filter_desc)]),
+    "mppi_unfiltered_control": (C.c_int, [_h, _dp]),
+    "mppi_safety_filter_stats": (C.c_int, [_h, _i64p, C.POINTER(C.c_float)]),
+    "mppi_dynamics_safety_filter": (C.c_int, [_h, C.POINTER(abi.mppi_safety_filter_desc), _dp, C.c_double, _dp]),
     "mppi_default_obstacle_config": (None, [C.POINTER(abi.mppi_obstacle_config)]),
     "mppi_set_obstacle_avoidance": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config)]),
     "mppi_get_obstacle_avoidance": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_obstacle_config)]),

@@ -167,6 +167,24 @@ class mppi_obstacle_config(C.Structure):
     _fields_ = [("limit", mppi_barrier), ("radii", _d * MPPI_OBSTACLE_POINTS)]
 
 
+class mppi_safety_filter_desc(C.Structure):
+    """TrajectorySafetyFilter::Configuration (frankaridgeback/safety.hpp:15-40) -> include/mppi_amd.h."""
+    _fields_ = [
+        ("position_minimum", _d * MPPI_FR_JOINTS),
+        ("position_maximum", _d * MPPI_FR_JOINTS),
+        ("velocity_minimum", _d * MPPI_FR_JOINTS),
+        ("velocity_maximum", _d * MPPI_FR_JOINTS),
+        ("acceleration_minimum", _d * MPPI_FR_JOINTS),
+        ("acceleration_maximum", _d * MPPI_FR_JOINTS),
+        ("reach_maximum", _d),
+        ("reach_minimum", _d),
+        ("limit_joints", C.c_int32),
+        ("limit_velocity", C.c_int32),
+        ("limit_acceleration", C.c_int32),
+        ("limit_reach", C.c_int32),
+    ]
+
+
 class mppi_assisted_manipulation_desc(C.Structure):
     _fields_ = [
         ("enable_joint_limit", C.c_int32),

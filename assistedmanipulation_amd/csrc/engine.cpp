@@ -188,6 +188,42 @@ struct DeviceBuf {
     size_t bytes = 0;
 };
 
+// mppi_safety_filter_desc: NaN or min > max is invalid, limit_reach unsupported; +-inf is "no limit"
+mppi_status check_safety_filter(const mppi_safety_filter_desc &f, std::string &why)
+{
+    if (f.limit_reach) {
+        why = "safety filter: limit_reach is not supported (it needs a task-space solve; the objectives carry a reach barrier)";
+        return MPPI_ERR_UNSUPPORTED;
+    }
+    const double *lo[3] = {f.position_minimum, f.velocity_minimum, f.acceleration_minimum};
+    const double *hi[3] = {f.position_maximum, f.velocity_maximum, f.acceleration_maximum};
+    static const char *names[3] = {"position", "velocity", "acceleration"};
+    for (int k = 0; k < 3; k++)
+        for (int i = 0; i < MPPI_FR_JOINTS; i++) {
+            if (std::isnan(lo[k][i]) || std::isnan(hi[k][i]) || lo[k][i] > hi[k][i]) {
+                why = std::string("safety filter: ") + names[k] + " limits of joint " + std::to_string(i) +
+                      " are NaN or minimum > maximum";
+                return MPPI_ERR_INVALID;
+            }
+        }
+    return MPPI_OK;
+}
+
+SafetyLimits safety_limits(const mppi_safety_filter_desc &f)
+{
+    SafetyLimits l{};
+    std::memcpy(l.position_minimum, f.position_minimum, sizeof(l.position_minimum));
+    std::memcpy(l.position_maximum, f.position_maximum, sizeof(l.position_maximum));
+    std::memcpy(l.velocity_minimum, f.velocity_minimum, sizeof(l.velocity_minimum));
+    std::memcpy(l.velocity_maximum, f.velocity_maximum, sizeof(l.velocity_maximum));
+    std::memcpy(l.acceleration_minimum, f.acceleration_minimum, sizeof(l.acceleration_minimum));
+    std::memcpy(l.acceleration_maximum, f.acceleration_maximum, sizeof(l.acceleration_maximum));
+    l.limit_joints = f.limit_joints != 0;
+    l.limit_velocity = f.limit_velocity != 0;
+    l.limit_acceleration = f.limit_acceleration != 0;
+    return l;
+}
+
 }  // namespace
 
 struct mppi_handle {
@@ -250,6 +286,16 @@ struct mppi_handle {
     mppi_obstacle ob_set[MPPI_MAX_OBSTACLES] = {};
     int32_t ob_count = 0;
     double ob_time = 0.0;
+    // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
+    // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
+    // (phase3_launch).  safety_ran: the last phase 3 ran it (d_out_stage holds that update's
+    // unfiltered plan); safety_changed: the steps it changed; safety_ms: its time under timing >= 1.
+    bool safety_on = false, safety_ran = false;
+    mppi_safety_filter_desc safety{};
+    double *d_out_stage = nullptr;   // [H C + 8]
+    hipEvent_t ev_sf[2] = {nullptr, nullptr};
+    int64_t safety_changed = 0;
+    float safety_ms = 0.0f;
     double *d_fc_rows = nullptr;    // [H][6] the caller's forecast table on the device (upload_steps)
     int64_t S = 0, K = 0, R = 0, H = 0, C = 0, X = 0;
     double dt = 0, gradient_step = 0, cost_scale = 0, gamma = 1;
@@ -1060,6 +1106,28 @@ mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_co
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
+                                        double *out12)
+{
+    if (!d || !filter || !control12 || !out12) return MPPI_ERR_INVALID;
+    std::string why;
+    const mppi_status cs = check_safety_filter(*filter, why);
+    if (cs != MPPI_OK) return dfail(d, cs, why);
+    if (!(dt > 0.0) || !std::isfinite(dt)) return dfail(d, MPPI_ERR_INVALID, "safety filter: the time step must be positive");
+    mppi_status st = obj_buffer(d, FR_C);
+    if (st != MPPI_OK) return st;
+    SafetyColumn c{};
+    std::memcpy(c.u, control12, sizeof(c.u));
+    std::memcpy(c.w, d->wrench_sum, sizeof(c.w));   // pending, not consumed
+    c.has_wrench = d->wrench_pending ? 1 : 0;
+    c.dt = dt;
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(launch_fr_safety_column(d->d_obj, d->d_model, safety_limits(*filter), c, d->d_buf, d->stream));
+    DHIP_TRY(hipMemcpyAsync(out12, d->d_buf, FR_C * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipStreamSynchronize(d->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_add_end_effector_simulated_wrench(mppi_dynamics *d, const double *wrench6)
 {
     if (!d || !wrench6) return MPPI_ERR_INVALID;
@@ -1287,9 +1355,11 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
         for (int64_t k = 0; k < h->H; k++) g[(size_t)k] = std::pow(h->gamma, (double)k);
         CREATE_TRY(hipMemcpy(h->d_gamma, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    CREATE_TRY(hipHostMalloc((void **)&h->h_out, (HC + 8) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    // (8 more slots behind the finish kernels' block: the safety filter's, fr_safety.hip)
+    CREATE_TRY(hipHostMalloc((void **)&h->h_out, (HC + 16) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
     CREATE_TRY(hipHostGetDevicePointer((void **)&h->h_out_dev, h->h_out, 0));
-    std::memset(h->h_out, 0, (HC + 8) * sizeof(double));   // the publish flag starts below every sequence
+    std::memset(h->h_out, 0, (HC + 16) * sizeof(double));   // the publish flag starts below every sequence
+    CREATE_TRY(dalloc(h, &h->d_out_stage, (size_t)(HC + 8)));
     CREATE_TRY(hipHostMalloc((void **)&h->h_opt, 8 * sizeof(double), hipHostMallocDefault));
     h->h_opt[0] = 0.0;
     CREATE_TRY(hipMemcpy(h->d_T, h->T.data(), h->T.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1420,6 +1490,8 @@ void mppi_destroy(mppi_handle *h)
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : h->ev_ring)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->ev_sf)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2117,7 +2189,9 @@ static FinishArgs finish_args(mppi_handle *h)
     f.sg_last_trim = h->d_sg_last;
     f.U = h->d_U;
     f.opt_cost = h->d_opt;
-    f.out = h->h_out_dev;   // the host block, written in place (no copy launch behind the finish)
+    // the host block, written in place (no copy launch behind the finish); with a safety filter the
+    // block is staged on the device and fr_safety_filter_kernel publishes it (phase3_launch)
+    f.out = h->safety_on ? h->d_out_stage : h->h_out_dev;
     f.seq = (double)(h->publish_seq + 1);   // != 0: the block's flag starts at 0
     f.x0 = h->d_x0;
     f.x0_opt = h->d_x0_opt;
@@ -2185,6 +2259,23 @@ static mppi_status phase3_launch(mppi_handle *h, double *seq_out)
     if (h->opt_state == mppi_handle::OPT_LAUNCHED) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_opt_done, 0));
     h->gargs.fin = finish_args(h);
     if (!h->graph_dry) HIP_TRY(launch_finish(h->gargs.fin, h->stream));
+    h->safety_ran = h->safety_on;
+    if (h->safety_on) {   // (never under graph_dry: graph_eligible)
+        SafetyArgs sa{};
+        sa.lim = safety_limits(h->safety);
+        sa.model = h->d_model;
+        sa.x0 = h->d_x0;
+        sa.stage = h->d_out_stage;
+        sa.wrench = h->simulated_wrench != MPPI_SIMULATED_WRENCH_OFF ? (const double *)(h->d_steps + h->H) : nullptr;
+        sa.U = h->d_U;
+        sa.out = h->h_out_dev;
+        sa.seq = h->gargs.fin.seq;
+        sa.dt = h->dt;
+        sa.H = (int)h->H;
+        if (h->timing >= 1) HIP_TRY(hipEventRecord(h->ev_sf[0], h->stream));
+        HIP_TRY(launch_fr_safety_filter(sa, h->stream));
+        if (h->timing >= 1) HIP_TRY(hipEventRecord(h->ev_sf[1], h->stream));
+    }
     const double seq = (double)(++h->publish_seq);
     *seq_out = seq;
     if (h->timing >= 2) HIP_TRY(hipEventRecord(h->ev[3], h->stream));
@@ -2272,6 +2363,12 @@ static mppi_status phase3_wait(mppi_handle *h, double seq)
         h->kernel_ms[7] = 0.0f;
         if (ar) (void)hipEventElapsedTime(&h->kernel_ms[7], h->ev[2], h->ev_ar);
     }
+    h->safety_changed = h->safety_ran ? (int64_t)h->h_out[HC + 8] : 0;
+    h->safety_ms = 0.0f;
+    if (h->safety_ran && h->timing >= 1) {
+        HIP_TRY(hipEventSynchronize(h->ev_sf[1]));
+        (void)hipEventElapsedTime(&h->safety_ms, h->ev_sf[0], h->ev_sf[1]);
+    }
     const bool all_nan = h->h_out[HC + 1] != 0.0;
     const bool sg_error = h->h_out[HC + 3] != 0.0;
     const int64_t waits = (int64_t)h->h_out[HC + 7];   // in-launch waits that gave up (the finish kernel)
@@ -2330,6 +2427,7 @@ mppi_status mppi_update_phase3(mppi_handle *h)
 static bool graph_eligible(const mppi_handle *h)
 {
     if (!h->graph_mode || h->timing != 0 || h->d_trace || h->host_trace) return false;
+    if (h->safety_on) return false;   // the safety filter's kernel is not a node of the captured chain
     if (sharded(h) && !h->comm) return false;   // the phase-split API: the caller's collectives
     if (!draw_ahead_possible(h) || tail_draws_disabled(h) || !fr_coop_costs_in_launch(h->env)) return false;
     if (h->fc.type != FC_NONE) return false;   // (the device forecast's sampling launch is not a node)
@@ -2618,6 +2716,80 @@ mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode)
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "simulated wrench: FrankaRidgeback handles only");
     *mode = h->simulated_wrench;
+    return MPPI_OK;
+}
+
+void mppi_default_safety_filter(mppi_safety_filter_desc *out)
+{
+    if (!out) return;
+    // robot.urdf's <limit lower upper velocity> of x, y, pivot, panda_joint1..7 and the two fingers
+    static const double lower[MPPI_FR_JOINTS] = {-10.0, -10.0, -10.0, -2.8973, -1.7628, -2.8973, -3.0718, -2.8973,
+                                                 -0.0175, -2.8973, -0.001, -0.001};
+    static const double upper[MPPI_FR_JOINTS] = {10.0, 10.0, 10.0, 2.8973, 1.7628, 2.8973, 0.0698, 2.8973, 3.7525,
+                                                 2.8973, 0.04, 0.04};
+    static const double velocity[MPPI_FR_JOINTS] = {1.0, 1.0, 1.0, 2.175, 2.175, 2.175, 2.175, 2.61, 2.61, 2.61, 0.3, 0.3};
+    std::memset(out, 0, sizeof(*out));
+    for (int i = 0; i < MPPI_FR_JOINTS; i++) {
+        out->position_minimum[i] = lower[i];
+        out->position_maximum[i] = upper[i];
+        out->velocity_minimum[i] = -velocity[i];
+        out->velocity_maximum[i] = velocity[i];
+        out->acceleration_minimum[i] = -INFINITY;   // robot.urdf has no acceleration limits
+        out->acceleration_maximum[i] = INFINITY;
+    }
+    out->reach_maximum = 0.8;   // safety.hpp:29-31
+    out->reach_minimum = 0.15;
+}
+
+mppi_status mppi_set_safety_filter(mppi_handle *h, const mppi_safety_filter_desc *filter)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "safety filter: FrankaRidgeback handles only");
+    if (h->phase_open) return fail(h, MPPI_ERR_INVALID, "the safety filter is set between updates");
+    if (!filter) {
+        h->safety_on = false;
+        return MPPI_OK;
+    }
+    std::string why;
+    const mppi_status st = check_safety_filter(*filter, why);
+    if (st != MPPI_OK) return fail(h, st, why);
+    if (h->H > SAFETY_MAX_H)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "safety filter: the horison is longer than " + std::to_string(SAFETY_MAX_H) + " steps");
+    if (!h->ev_sf[0]) {
+        HIP_TRY(hipSetDevice(h->device));
+        for (auto &e : h->ev_sf) HIP_TRY(hipEventCreate(&e));
+    }
+    h->safety = *filter;
+    h->safety_on = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_safety_filter(mppi_handle *h, int *enabled, mppi_safety_filter_desc *out)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "safety filter: FrankaRidgeback handles only");
+    *enabled = h->safety_on ? 1 : 0;
+    if (out && h->safety_on) *out = h->safety;
+    return MPPI_OK;
+}
+
+mppi_status mppi_unfiltered_control(mppi_handle *h, double *out)
+{
+    if (!h || !out) return MPPI_ERR_INVALID;
+    if (!h->safety_ran) return mppi_optimal_control(h, out);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, h->d_out_stage, (size_t)(h->H * h->C) * sizeof(double), hipMemcpyDeviceToHost));
+    return MPPI_OK;
+}
+
+mppi_status mppi_safety_filter_stats(mppi_handle *h, int64_t *changed_steps, float *kernel_ms)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (changed_steps) *changed_steps = h->safety_changed;
+    if (kernel_ms) *kernel_ms = h->safety_ms;
     return MPPI_OK;
 }
 

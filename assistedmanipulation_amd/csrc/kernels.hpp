@@ -409,6 +409,36 @@ struct ObjArgs {
     int has_wrench, wrench_rows;
 };
 hipError_t launch_fr_object(const ObjArgs &a, hipStream_t s);
+
+// The trajectory safety filter (fr_safety.hip; mppi_set_safety_filter, mppi_dynamics_safety_filter):
+// per-joint limits and the three switches of mppi_safety_filter_desc (limit_reach is refused by the host).
+struct SafetyLimits {
+    double position_minimum[FR_NB], position_maximum[FR_NB];
+    double velocity_minimum[FR_NB], velocity_maximum[FR_NB];
+    double acceleration_minimum[FR_NB], acceleration_maximum[FR_NB];
+    int limit_joints, limit_velocity, limit_acceleration, pad;
+};
+constexpr int SAFETY_MAX_H = 384;   // the plan, its wrench rows and the step's scratch share 64 KiB of LDS
+struct SafetyArgs {
+    SafetyLimits lim;
+    const DevModel *model;
+    const double *x0;       // the update's state
+    const double *stage;    // [H C + 8] the finish kernel's block: the unfiltered plan, its status words
+    const double *wrench;   // [H][FR_WRENCH_ROW] the update's simulated-wrench rows, or null
+    double *U;              // [H][C] the plan on the device, rewritten
+    double *out;            // the mapped host block [H C + 16]: the filtered plan, the forwarded status
+                            // words, [H C + 8] the steps the filter changed, [H C + 6] the flag, last
+    double seq, dt;
+    int H;
+};
+struct SafetyColumn {
+    double u[FR_C], w[6], dt;
+    int has_wrench, pad;
+};
+size_t fr_safety_lds_bytes(int H);
+hipError_t launch_fr_safety_filter(const SafetyArgs &a, hipStream_t s);
+hipError_t launch_fr_safety_column(const DevPinocchio *obj, const DevModel *model, const SafetyLimits &lim, const SafetyColumn &c,
+                                   double *out12, hipStream_t s);
 // The update's simulated-wrench rows, out[H][FR_WRENCH_ROW]: source WT_CONST the wrench w in every row,
 // WT_TABLE row k of table[H][6], WT_FORECAST forecast(t0 + k dt) as the step constants sample it
 enum WrenchSource : int { WT_CONST = 0, WT_TABLE = 1, WT_FORECAST = 2 };

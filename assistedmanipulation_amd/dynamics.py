@@ -152,6 +152,17 @@ class PinocchioDynamicsObject:
         self._check(self._L.mppi_dynamics_get_end_effector_simulated_wrench(self._h, _p(o)))
         return o
 
+    def safety_filter(self, filter, control, dt):
+        """mppi_dynamics_safety_filter: the TrajectorySafetyFilter `filter` on one control (12) at the
+        object's current joint position and velocity with time step `dt`; the filtered control.  A
+        wrench added since the last step is included and not consumed."""
+        u = np.ascontiguousarray(control, dtype=np.float64).reshape(-1)
+        assert u.size == abi.MPPI_FR_CONTROL
+        c = filter.to_c()
+        out = np.zeros(abi.MPPI_FR_CONTROL)
+        self._check(self._L.mppi_dynamics_safety_filter(self._h, C.byref(c), _p(u), float(dt), _p(out)))
+        return out
+
     def set_simulated_wrench(self, mode):
         """mppi_dynamics_set_simulated_wrench (abi.MPPI_SIMULATED_WRENCH_OFF / _ON): whether
         forecast() adds its wrench rows before each step."""

@@ -20,6 +20,7 @@ from . import abi
 from ._lib import load
 from .obstacles import ObstacleAvoidance, obstacle_from_c, obstacles_to_c
 from .config import Configuration
+from .safety import TrajectorySafetyFilter
 
 
 class EngineError(RuntimeError):
@@ -233,8 +234,9 @@ class Trajectory:
         self._state_ptr = _p(self._state_buf)
 
     @staticmethod
-    def create(configuration: Configuration, dynamics: Dynamics, cost: Cost, device=0):
-        """Trajectory::create — None (and a message on stderr) on invalid input."""
+    def create(configuration: Configuration, dynamics: Dynamics, cost: Cost, device=0, filter=None):
+        """Trajectory::create — None (and a message on stderr) on invalid input.  `filter`: a
+        TrajectorySafetyFilter applied to every update's plan, or None."""
         L = load()
         cfg, keep = configuration.to_c()
         dd, cd = dynamics.descriptor(), cost.descriptor()
@@ -251,6 +253,13 @@ class Trajectory:
         sw = getattr(dynamics, "simulated_wrench", None)
         if sw is not None:   # FrankaRidgebackDynamics(simulated_wrench=...)
             t.set_simulated_wrench(FrankaRidgebackDynamics.SIMULATED_WRENCH_MODES[sw])
+        if filter is not None:
+            try:
+                t.set_safety_filter(filter)
+            except EngineError as e:   # the reference's create prints and returns nullptr
+                print(str(e), file=sys.stderr)
+                t.close()
+                return None
         return t
 
     # -- lifecycle --------------------------------------------------------------------------
@@ -316,6 +325,38 @@ class Trajectory:
             return abi.MPPI_SIMULATED_WRENCH_OFF
         self._check(st)
         return m.value
+
+    def set_safety_filter(self, filter):
+        """mppi_set_safety_filter: a TrajectorySafetyFilter, or None to turn it off; between any two
+        updates.  FrankaRidgeback handles only.  With a filter set every update publishes the
+        filtered plan (and does not run as a hipGraph)."""
+        if filter is None:
+            self._check(self._L.mppi_set_safety_filter(self._h, None))
+            return
+        c = filter.to_c()
+        self._check(self._L.mppi_set_safety_filter(self._h, C.byref(c)))
+
+    @property
+    def safety_filter(self):
+        """The TrajectorySafetyFilter the handle runs with, or None."""
+        on, c = C.c_int(0), abi.mppi_safety_filter_desc()
+        st = self._L.mppi_get_safety_filter(self._h, C.byref(on), C.byref(c))
+        if st == abi.MPPI_ERR_UNSUPPORTED:
+            return None
+        self._check(st)
+        return TrajectorySafetyFilter.from_c(c) if on.value else None
+
+    def unfiltered_control(self):
+        """mppi_unfiltered_control: the last update's plan as optimise() left it, before the safety
+        filter, (H, C) like get_optimal_rollout (which it equals without a filter)."""
+        return self._vec(self._L.mppi_unfiltered_control, self.C * self.H).reshape(self.H, self.C)
+
+    def safety_filter_stats(self):
+        """{"changed_steps": steps of the last update's plan the filter changed, "kernel_ms": the
+        filter kernel's time (0 unless set_timing(1) or (2))}."""
+        n, ms = C.c_int64(0), C.c_float(0.0)
+        self._check(self._L.mppi_safety_filter_stats(self._h, C.byref(n), C.byref(ms)))
+        return {"changed_steps": n.value, "kernel_ms": ms.value}
 
     def set_obstacle_avoidance(self, config=None):
         """mppi_set_obstacle_avoidance: sphere and half-space obstacles in the rollouts' objective,

@@ -459,6 +459,45 @@ mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, i
 mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *count, double *time);
 mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost);
 
+/* The trajectory safety filter: FrankaRidgeback::TrajectorySafetyFilter::Configuration
+ * (frankaridgeback/safety.hpp:15-40) field for field.  The reference declares the class and leaves
+ * its methods empty; here the configuration is live, opt-in (no filter unless one is set).  The
+ * filter is stateless and acts on joints 0..9 (the fingers are not actuated).  Column k of the new
+ * plan U* is corrected, while the plan is rolled out from the update's state with the handle's own
+ * time step, so that the state after the step meets the enabled limits; the switches are applied
+ * in the order position, velocity, acceleration and a later one wins (a position limit holds only
+ * where the velocity and acceleration limits do not bind: there is no braking-distance rule).  The
+ * arm's torque is corrected through the mass matrix with the other joints' torque untouched, the
+ * base's velocity command directly.  A column that no limit binds is returned bit for bit, and U*
+ * is not clamped to control_min / control_max again.  A limit may be +-inf (no limit on that side);
+ * NaN, or a minimum above its maximum, is MPPI_ERR_INVALID.  limit_reach is refused
+ * (MPPI_ERR_UNSUPPORTED): it needs a task-space solve, and both objectives carry a reach barrier.
+ * The definition: DESIGN.md section 1, "Safety filter".
+ *
+ * mppi_set_safety_filter: FrankaRidgeback handles only (MPPI_ERR_UNSUPPORTED otherwise, and for a
+ * horison past 384 steps); NULL turns the filter off; it may be set or changed between any two
+ * updates.  With a filter set the update publishes the filtered plan only (mppi_get,
+ * mppi_optimal_control, the optimal rollout and the next update all see it), mppi_unfiltered_control
+ * returns the plan as optimise() left it (equal to mppi_optimal_control without a filter), and
+ * updates do not run as a hipGraph.  mppi_safety_filter_stats: the number of steps of the last
+ * update's plan the filter changed, and the filter kernel's time in ms (0 unless mppi_set_timing
+ * is 1 or 2); either pointer may be NULL.
+ * Added after ABI version 5 without a version change (one new struct, new symbols): detect by symbol. */
+typedef struct mppi_safety_filter_desc {
+    double position_minimum[MPPI_FR_JOINTS], position_maximum[MPPI_FR_JOINTS];
+    double velocity_minimum[MPPI_FR_JOINTS], velocity_maximum[MPPI_FR_JOINTS];
+    double acceleration_minimum[MPPI_FR_JOINTS], acceleration_maximum[MPPI_FR_JOINTS];
+    double reach_maximum, reach_minimum;
+    int32_t limit_joints, limit_velocity, limit_acceleration, limit_reach;
+} mppi_safety_filter_desc;
+/* Every switch off; robot.urdf's joint position limits and velocity limits (base 1, arm 2.175 /
+ * 2.61, fingers 0.3); robot.urdf has no acceleration limits: +-inf; reach 0.8 / 0.15. */
+void mppi_default_safety_filter(mppi_safety_filter_desc *out);
+mppi_status mppi_set_safety_filter(mppi_handle *h, const mppi_safety_filter_desc *filter);
+mppi_status mppi_get_safety_filter(mppi_handle *h, int *enabled, mppi_safety_filter_desc *out);
+mppi_status mppi_unfiltered_control(mppi_handle *h, double *control_CxH);
+mppi_status mppi_safety_filter_stats(mppi_handle *h, int64_t *changed_steps, float *kernel_ms);
+
 /* Phase-split update for callers that run the collectives themselves (multi-GPU with an
  * external communicator, or two shards on one device in tests).  Between phase 1 and 2 the
  * caller all-reduces (sum) the R + 1 doubles of mppi_device_costs(h) - the R costs and slot R,
@@ -698,6 +737,11 @@ mppi_status mppi_dynamics_get_end_effector_simulated_wrench(mppi_dynamics *d, do
  * reference's stub).  An explicit add is live in either mode. */
 mppi_status mppi_dynamics_set_simulated_wrench(mppi_dynamics *d, int mode);
 mppi_status mppi_dynamics_get_simulated_wrench(mppi_dynamics *d, int *mode);
+/* The safety filter (mppi_safety_filter_desc, above) on one control at the object's current joint
+ * position and velocity with time step dt: out12 is the filtered control.  A wrench added since the
+ * last step joins the torque as the step would apply it, and is not consumed. */
+mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12,
+                                        double dt, double *out12);
 /* forecast(t0 + k dt) for k < steps of the handle's attached forecast (steps x 6). */
 mppi_status mppi_forecast_table(mppi_handle *h, double t0, double dt, int64_t steps, double *out);
 

@@ -136,6 +136,14 @@ public:
     virtual void set_optimal_terms(const double *) {}
 };
 
+// A trajectory filter the device can run: it describes itself as the engine's safety filter
+// (mppi_safety_filter_desc).  Its own filter() stays host-callable; updates never call back into it.
+class DeviceFilter {
+public:
+    virtual ~DeviceFilter() = default;
+    virtual bool describe(mppi_safety_filter_desc &out) const = 0;
+};
+
 struct Configuration {
     std::vector<double> initial_state;
     std::int64_t rollouts = 0;
@@ -169,7 +177,12 @@ public:
                                               std::unique_ptr<Cost> &&cost, std::unique_ptr<Filter> &&filter = nullptr,
                                               int device = 0)
     {
-        if (filter) {   // the reference's Actor passes nullptr (actor.cpp:100); the safety filter is stubs
+        // the reference's Actor passes nullptr (actor.cpp:100).  A filter that describes itself
+        // (mppi::DeviceFilter: FrankaRidgeback::TrajectorySafetyFilter) runs on the device; any other
+        // would have to be called from the update and is refused.
+        mppi_safety_filter_desc fd{};
+        const DeviceFilter *fdev = dynamic_cast<const DeviceFilter *>(filter.get());
+        if (filter && (!fdev || !fdev->describe(fd))) {
             std::cerr << "mppi_amd: trajectory filters are not supported on the device" << std::endl;
             return nullptr;
         }
@@ -222,7 +235,14 @@ public:
             mppi_destroy(h);
             return nullptr;
         }
-        return std::unique_ptr<Trajectory>(new Trajectory(h, configuration, std::move(dynamics), std::move(cost)));
+        if (filter && mppi_set_safety_filter(h, &fd) != MPPI_OK) {
+            std::cerr << mppi_last_error(h) << std::endl;
+            mppi_destroy(h);
+            return nullptr;
+        }
+        std::unique_ptr<Trajectory> t(new Trajectory(h, configuration, std::move(dynamics), std::move(cost)));
+        t->m_filter = std::move(filter);
+        return t;
     }
 
     ~Trajectory() { mppi_destroy(m_h); }
@@ -244,6 +264,29 @@ public:
     {
         int mode = MPPI_SIMULATED_WRENCH_OFF;
         return mppi_get_simulated_wrench(m_h, &mode) == MPPI_OK ? mode : MPPI_SIMULATED_WRENCH_OFF;
+    }
+    // The safety filter (mppi_set_safety_filter; nullptr: off), between any two updates; false and
+    // a message on stderr when it is refused
+    bool set_safety_filter(const mppi_safety_filter_desc *filter)
+    {
+        if (mppi_set_safety_filter(m_h, filter) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // whether one is set, and its configuration
+    bool safety_filter(mppi_safety_filter_desc *out = nullptr) const
+    {
+        int on = 0;
+        return mppi_get_safety_filter(m_h, &on, out) == MPPI_OK && on != 0;
+    }
+    // the plan as optimise() left it, before the safety filter (C x H column-major, like get_optimal_rollout)
+    std::vector<double> get_unfiltered_rollout() const { return fetch(mppi_unfiltered_control, (size_t)(m_C * m_H)); }
+    // the steps of the last update's plan the safety filter changed
+    std::int64_t safety_filter_changed_steps() const
+    {
+        int64_t n = 0;
+        (void)mppi_safety_filter_stats(m_h, &n, nullptr);
+        return n;
     }
     // Obstacle avoidance (mppi_set_obstacle_avoidance; nullptr: the default configuration): sphere
     // and half-space obstacles in the rollouts' objective.  A FrankaRidgeback trajectory in the
@@ -420,6 +463,7 @@ private:
     Configuration m_configuration;
     std::unique_ptr<Dynamics> m_dynamics;
     std::unique_ptr<Cost> m_cost;
+    std::unique_ptr<Filter> m_filter;   // the described filter create() took (kept alive, never called)
     int64_t m_R = 0, m_H = 0, m_C = 0, m_X = 0;
     std::vector<double> m_rolled_out_state;
     double m_update_last = 0;
@@ -602,6 +646,15 @@ public:
         return w;
     }
     int simulated_wrench() const override { return m_configuration.simulated_wrench; }
+    // the safety filter on one control at this object's joint position and velocity
+    // (mppi_dynamics_safety_filter); a pending simulated wrench is included and not consumed
+    mppi::VectorXd safety_filter(const mppi_safety_filter_desc &filter, const mppi::VectorXd &control, double dt)
+    {
+        if (control.size() != MPPI_FR_CONTROL) throw std::invalid_argument("control has the wrong dimension");
+        mppi::VectorXd out(MPPI_FR_CONTROL);
+        check(mppi_dynamics_safety_filter(object(), &filter, control.data(), dt, out.data()));
+        return out;
+    }
     void set_forecast(WrenchSource source) { m_forecast = std::move(source); }
     const WrenchSource &get_forecast() const { return m_forecast; }
 
@@ -642,6 +695,95 @@ private:
     mppi_dynamics *m_obj = nullptr;
     mppi::VectorXd m_state = mppi::VectorXd(MPPI_FR_STATE);
     WrenchSource m_forecast;
+};
+
+// FrankaRidgeback::TrajectorySafetyFilter (frankaridgeback/safety.hpp:11-61), whose methods the
+// reference leaves empty: joint position, velocity and acceleration limits on the plan (mppi_amd.h,
+// mppi_safety_filter_desc).  Passed to mppi::Trajectory::create it runs on the device inside every
+// update with the trajectory's own time step.  filter() is the same filter on one control, run
+// through mppi_dynamics_safety_filter on a dynamics object this filter owns, with
+// Configuration::time_step (a field the reference's Configuration does not have: the reference's
+// filter() is not told the step).  The filter is stateless: reset() does nothing, the time is unused.
+class TrajectorySafetyFilter : public mppi::Filter, public mppi::DeviceFilter {
+public:
+    struct Configuration {
+        std::array<double, MPPI_FR_JOINTS> position_minimum, position_maximum;
+        std::array<double, MPPI_FR_JOINTS> velocity_minimum, velocity_maximum;
+        std::array<double, MPPI_FR_JOINTS> acceleration_minimum, acceleration_maximum;
+        double reach_maximum = 0.8;
+        double reach_minimum = 0.15;
+        bool limit_joints = false;
+        bool limit_velocity = false;
+        bool limit_acceleration = false;
+        bool limit_reach = false;
+        double time_step = 0.01;   // of the host-callable filter() only
+        int device = 0;
+    };
+    // robot.urdf's position and velocity limits, no acceleration limits, every switch off
+    static Configuration default_configuration()
+    {
+        mppi_safety_filter_desc d;
+        mppi_default_safety_filter(&d);
+        Configuration c;
+        for (int i = 0; i < MPPI_FR_JOINTS; i++) {
+            c.position_minimum[i] = d.position_minimum[i];
+            c.position_maximum[i] = d.position_maximum[i];
+            c.velocity_minimum[i] = d.velocity_minimum[i];
+            c.velocity_maximum[i] = d.velocity_maximum[i];
+            c.acceleration_minimum[i] = d.acceleration_minimum[i];
+            c.acceleration_maximum[i] = d.acceleration_maximum[i];
+        }
+        return c;
+    }
+    static std::unique_ptr<TrajectorySafetyFilter> create(Configuration &&configuration)
+    {
+        return std::unique_ptr<TrajectorySafetyFilter>(new TrajectorySafetyFilter(std::move(configuration)));
+    }
+    bool describe(mppi_safety_filter_desc &out) const override
+    {
+        out = mppi_safety_filter_desc{};
+        for (int i = 0; i < MPPI_FR_JOINTS; i++) {
+            out.position_minimum[i] = m_configuration.position_minimum[i];
+            out.position_maximum[i] = m_configuration.position_maximum[i];
+            out.velocity_minimum[i] = m_configuration.velocity_minimum[i];
+            out.velocity_maximum[i] = m_configuration.velocity_maximum[i];
+            out.acceleration_minimum[i] = m_configuration.acceleration_minimum[i];
+            out.acceleration_maximum[i] = m_configuration.acceleration_maximum[i];
+        }
+        out.reach_maximum = m_configuration.reach_maximum;
+        out.reach_minimum = m_configuration.reach_minimum;
+        out.limit_joints = m_configuration.limit_joints;
+        out.limit_velocity = m_configuration.limit_velocity;
+        out.limit_acceleration = m_configuration.limit_acceleration;
+        out.limit_reach = m_configuration.limit_reach;
+        return true;
+    }
+    mppi::VectorXd filter(mppi::Ref<mppi::VectorXd> state, mppi::Ref<mppi::VectorXd> control, double time) override
+    {
+        if (state.size() != MPPI_FR_STATE) throw std::invalid_argument("state has the wrong dimension");
+        if (control.size() != MPPI_FR_CONTROL) throw std::invalid_argument("control has the wrong dimension");
+        if (!m_dynamics) {
+            PinocchioDynamics::Configuration c;
+            c.device = m_configuration.device;
+            m_dynamics = PinocchioDynamics::create(c);
+        }
+        mppi::VectorXd x(MPPI_FR_STATE), u(MPPI_FR_CONTROL);
+        for (int i = 0; i < MPPI_FR_STATE; i++) x[i] = state[i];
+        for (int i = 0; i < MPPI_FR_CONTROL; i++) u[i] = control[i];
+        m_dynamics->set_state(x, time);
+        mppi_safety_filter_desc d;
+        describe(d);
+        mppi::VectorXd out = m_dynamics->safety_filter(d, u, m_configuration.time_step);
+        for (int i = 0; i < MPPI_FR_CONTROL; i++) control[i] = out[i];   // in place, as Trajectory::filter() uses it
+        return out;
+    }
+    void reset(mppi::Ref<mppi::VectorXd>, double) override {}
+    const Configuration &configuration() const { return m_configuration; }
+
+private:
+    explicit TrajectorySafetyFilter(Configuration &&c) : m_configuration(std::move(c)) {}
+    Configuration m_configuration;
+    std::unique_ptr<PinocchioDynamics> m_dynamics;
 };
 
 // FrankaRidgeback::AssistedManipulation (objective/assisted_manipulation.hpp:16-398): Configuration
