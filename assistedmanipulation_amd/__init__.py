@@ -18,7 +18,9 @@ from .trajectory import (AssistedManipulation, Cost, Dynamics, EngineError, Trac
                          FrankaRidgebackDynamics, PointMassDynamics, Predicted, QuadraticCost, Trajectory,
                          comm_unique_id, shard_range)
 
-from .obstacles import HalfSpaceObstacle, ObstacleAvoidance, SphereObstacle, obstacle_clearance  # noqa: E402
+from .obstacles import (CapsuleObstacle, HalfSpaceObstacle, ObstacleAvoidance, ObstacleCapsules, SphereObstacle,  # noqa: E402
+                        MASK_ALL, MASK_SEGMENTS, mask_segment, obstacle_clearance, obstacle_from_c, obstacles_to_c,
+                        segment_distance)
 from .safety import TrajectorySafetyFilter  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
 from .dynamics import DynamicsForecast, EndEffectorState, PinocchioDynamicsObject, evaluate_cost  # noqa: E402
@@ -30,5 +32,6 @@ __all__ = [
     "kalman_forecast_configuration", "AssistedManipulation", "TrackPoint", "Cost", "Dynamics",
     "EngineError", "FrankaRidgebackDynamics", "PointMassDynamics", "QuadraticCost", "Trajectory",
     "comm_unique_id", "shard_range", "Predicted", "ObstacleAvoidance", "SphereObstacle", "HalfSpaceObstacle",
-    "obstacle_clearance", "TrajectorySafetyFilter",
+    "obstacle_clearance", "TrajectorySafetyFilter", "CapsuleObstacle", "ObstacleCapsules", "MASK_ALL", "MASK_SEGMENTS",
+    "mask_segment", "obstacle_from_c", "obstacles_to_c", "segment_distance",
 ]

@@ -112,6 +112,11 @@ PROTOTYPES = {
     "mppi_optimal_obstacle_cost": (C.c_int, [_h, _dp]),
     "mppi_dynamics_obstacle_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_obstacle), C.c_int32,
                                               C.c_double, _dp]),
+    "mppi_default_capsule_config": (None, [C.POINTER(abi.mppi_capsule_config)]),
+    "mppi_set_obstacle_capsules": (C.c_int, [_h, C.POINTER(abi.mppi_capsule_config)]),
+    "mppi_get_obstacle_capsules": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_capsule_config)]),
+    "mppi_dynamics_capsule_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_capsule_config),
+                                             C.POINTER(abi.mppi_obstacle), C.c_int32, C.c_double, _dp]),
 }
 
 _lib = None

@@ -70,6 +70,14 @@ MPPI_OBSTACLE_POINTS = 9
 MPPI_OBSTACLE_SPHERE = 0
 MPPI_OBSTACLE_HALF_SPACE = 1
 MPPI_OBSTACLE_MASK_ALL = 0x1FF
+# mppi_set_obstacle_capsules
+MPPI_OBSTACLE_CAPSULE = 2
+MPPI_OBSTACLE_SEGMENTS = 8
+MPPI_OBSTACLE_MASK_SEGMENTS = 0xFF0000
+
+
+def MPPI_OBSTACLE_MASK_SEGMENT(s):
+    return 1 << (16 + s)
 # One row of mppi_predicted_optimal / mppi_predicted_rollouts (MPPI_PRED_*): q_k, qd_k, the tank level,
 # then the grasp-frame, arm-mount and link positions at q_k
 MPPI_PRED_Q, MPPI_PRED_QD, MPPI_PRED_ENERGY, MPPI_PRED_EE, MPPI_PRED_ARM_MOUNT, MPPI_PRED_LINKS = 0, 12, 24, 25, 28, 31
@@ -165,6 +173,10 @@ class mppi_obstacle(C.Structure):
 
 class mppi_obstacle_config(C.Structure):
     _fields_ = [("limit", mppi_barrier), ("radii", _d * MPPI_OBSTACLE_POINTS)]
+
+
+class mppi_capsule_config(C.Structure):
+    _fields_ = [("segment_radii", _d * MPPI_OBSTACLE_SEGMENTS)]
 
 
 class mppi_safety_filter_desc(C.Structure):

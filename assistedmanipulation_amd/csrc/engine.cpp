@@ -114,8 +114,20 @@ bool check_obstacle_config(const mppi_obstacle_config &c, std::string &why)
     return true;
 }
 
-// mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set
-bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why)
+// mppi_set_obstacle_capsules' configuration: finite radii >= 0
+bool check_capsule_config(const mppi_capsule_config &c, std::string &why)
+{
+    for (int s = 0; s < MPPI_OBSTACLE_SEGMENTS; s++)
+        if (!std::isfinite(c.segment_radii[s]) || c.segment_radii[s] < 0.0) {
+            why = "obstacle capsules: segment_radii[" + std::to_string(s) + "] must be finite and >= 0";
+            return false;
+        }
+    return true;
+}
+
+// mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set (capsules: a capsule handle's, or
+// mppi_dynamics_capsule_cost's - the capsule kind and the segment bits of a mask are legal)
+bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why, bool capsules = false)
 {
     if (count < 0 || count > MPPI_MAX_OBSTACLES) {
         why = "obstacles: count must be in [0, " + std::to_string(MPPI_MAX_OBSTACLES) + "]";
@@ -132,12 +144,20 @@ bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::
     for (int32_t o = 0; o < count; o++) {
         const mppi_obstacle &b = set[o];
         const std::string at = "obstacle " + std::to_string(o) + ": ";
-        if (b.kind != MPPI_OBSTACLE_SPHERE && b.kind != MPPI_OBSTACLE_HALF_SPACE) {
+        if (b.kind == MPPI_OBSTACLE_CAPSULE && !capsules) {
+            why = at + "the capsule kind needs obstacle capsules (mppi_set_obstacle_capsules)";
+            return false;
+        }
+        if (b.kind != MPPI_OBSTACLE_SPHERE && b.kind != MPPI_OBSTACLE_HALF_SPACE && b.kind != MPPI_OBSTACLE_CAPSULE) {
             why = at + "unknown kind";
             return false;
         }
-        if (b.mask & ~MPPI_OBSTACLE_MASK_ALL) {
+        if (!capsules && (b.mask & ~MPPI_OBSTACLE_MASK_ALL)) {
             why = at + "mask has bits above bit 8";
+            return false;
+        }
+        if (capsules && (b.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS))) {
+            why = at + "mask has bits outside the points (0..8) and the segments (16..23)";
             return false;
         }
         bool finite = std::isfinite(b.radius);
@@ -163,8 +183,10 @@ bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::
 
 // The device table of a configuration and a set at update time t0 (engine_types.hpp ObstacleTable)
 void fill_obstacle_table(ObstacleTable &t, const mppi_obstacle_config &c, const mppi_obstacle *set, int32_t count, double t0,
-                                double t_ref)
+                                double t_ref, const mppi_capsule_config *capsules = nullptr)
 {
+    if (capsules)
+        for (int s = 0; s < OB_SEGMENTS; s++) t.seg_radii[s] = capsules->segment_radii[s];
     t.limit = DevBarrier{c.limit.bound, c.limit.scale, c.limit.maximum_cost};
     for (int i = 0; i < OB_POINTS; i++) t.radii[i] = c.radii[i];
     t.t0 = t0;
@@ -178,7 +200,7 @@ void fill_obstacle_table(ObstacleTable &t, const mppi_obstacle_config &c, const 
             d.normal[i] = set[o].normal[i];
         }
         d.radius = set[o].radius;
-        d.kind = set[o].kind == MPPI_OBSTACLE_HALF_SPACE ? OB_HALF_SPACE : OB_SPHERE;
+        d.kind = set[o].kind == MPPI_OBSTACLE_HALF_SPACE ? OB_HALF_SPACE : (set[o].kind == MPPI_OBSTACLE_CAPSULE ? OB_CAPSULE : OB_SPHERE);
         d.mask = set[o].mask;
     }
 }
@@ -286,6 +308,10 @@ struct mppi_handle {
     mppi_obstacle ob_set[MPPI_MAX_OBSTACLES] = {};
     int32_t ob_count = 0;
     double ob_time = 0.0;
+    // mppi_set_obstacle_capsules: the segments' radii (the table's tail) and the capsule kernels
+    // (FR_LINKS_CAPSULES), fixed once enabled like avoidance itself
+    bool obstacle_capsules = false;
+    mppi_capsule_config cap_config{};
     // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
     // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
     // (phase3_launch).  safety_ran: the last phase 3 ran it (d_out_stage holds that update's
@@ -1106,6 +1132,32 @@ mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_co
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_capsule_config *capsules,
+                                       const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost)
+{
+    if (!d || !cost) return MPPI_ERR_INVALID;
+    if (d->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return dfail(d, MPPI_ERR_INVALID, "capsule cost needs the kinematic link-position model (mppi_dynamics_set_link_positions)");
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    mppi_capsule_config cc;
+    if (capsules) cc = *capsules;
+    else mppi_default_capsule_config(&cc);
+    std::string why;
+    if (!check_obstacle_config(c, why) || !check_capsule_config(cc, why) || !check_obstacles(obstacles, count, elapsed, why, true))
+        return dfail(d, MPPI_ERR_INVALID, why);
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    ObstacleTable t{};
+    fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0, &cc);   // tau = elapsed
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(launch_fr_object_obstacles(d->d_obj, t, d->d_buf, d->stream, true));
+    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipStreamSynchronize(d->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
                                         double *out12)
 {
@@ -1856,7 +1908,7 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
 // FrRolloutArgs::link_positions of the handle's launches
 static int launch_link_mode(const mppi_handle *h)
 {
-    if (h->obstacle_avoidance) return FR_LINKS_OBSTACLES;
+    if (h->obstacle_avoidance) return h->obstacle_capsules ? FR_LINKS_CAPSULES : FR_LINKS_OBSTACLES;
     return h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? FR_LINKS_KINEMATIC : FR_LINKS_ZERO;
 }
 
@@ -1957,7 +2009,7 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
 {
     h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
     ObstacleTable t{};
-    fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time);
+    fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time, h->obstacle_capsules ? &h->cap_config : nullptr);
     HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
     return MPPI_OK;
 }
@@ -2833,7 +2885,7 @@ mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, i
     if (!h) return MPPI_ERR_INVALID;
     if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
     std::string why;
-    if (!check_obstacles(obstacles, count, time, why)) return fail(h, MPPI_ERR_INVALID, why);
+    if (!check_obstacles(obstacles, count, time, why, h->obstacle_capsules)) return fail(h, MPPI_ERR_INVALID, why);
     for (int32_t o = 0; o < count; o++) h->ob_set[o] = obstacles[o];
     h->ob_count = count;
     h->ob_time = time;
@@ -2848,6 +2900,37 @@ mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *co
     if (time) *time = h->ob_time;
     if (out16)
         for (int32_t o = 0; o < h->ob_count; o++) out16[o] = h->ob_set[o];
+    return MPPI_OK;
+}
+
+void mppi_default_capsule_config(mppi_capsule_config *out)
+{
+    if (!out) return;
+    for (int s = 0; s < MPPI_OBSTACLE_SEGMENTS; s++) out->segment_radii[s] = 0.1;
+}
+
+mppi_status mppi_set_obstacle_capsules(mppi_handle *h, const mppi_capsule_config *config)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->obstacle_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "obstacle capsules: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
+    // the capsule kernels are part of the launch plan and of a captured graph, like the obstacle kernels
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "obstacle capsules are enabled before the first update");
+    mppi_capsule_config c;
+    if (config) c = *config;
+    else mppi_default_capsule_config(&c);
+    std::string why;
+    if (!check_capsule_config(c, why)) return fail(h, MPPI_ERR_INVALID, why);
+    h->cap_config = c;
+    h->obstacle_capsules = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_obstacle_capsules(mppi_handle *h, int *enabled, mppi_capsule_config *out)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->obstacle_capsules ? 1 : 0;
+    if (h->obstacle_capsules && out) *out = h->cap_config;
     return MPPI_OK;
 }
 
@@ -3141,7 +3224,7 @@ mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
     if (st != MPPI_OK) return st;
     // (the row's own update's table: behind opt_steps)
     HIP_TRY(launch_fr_obstacle_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
-                                     h->stream_opt));
+                                     h->stream_opt, h->obstacle_capsules));
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->h_opt[1];

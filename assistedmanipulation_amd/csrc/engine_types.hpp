@@ -95,7 +95,12 @@ struct StepConst {
 // launch_obstacle_table), so the filter() row reads the set and the time of the update it belongs
 // to and a replayed graph needs no node for it.  OB_POINTS: the eight sphere links, then the end effector.
 constexpr int OB_MAX = 16, OB_POINTS = 9;
-constexpr int OB_SPHERE = 0, OB_HALF_SPACE = 1;
+constexpr int OB_SPHERE = 0, OB_HALF_SPACE = 1, OB_CAPSULE = 2;
+// Capsules (mppi_set_obstacle_capsules): robot segment s joins points s and s + 1, mask bit
+// OB_SEGMENT_BIT0 + s; its radius is in the table's tail, behind everything the point kernels read.
+constexpr int OB_SEGMENTS = 8, OB_SEGMENT_BIT0 = 16;
+// what the objective's obstacle term tests: nothing, the nine points, or points and segments
+constexpr int OB_TERM_NONE = 0, OB_TERM_POINTS = 1, OB_TERM_CAPSULES = 2;
 struct DevObstacle {
     double position[3], velocity[3], normal[3], radius;
     int kind;
@@ -107,6 +112,7 @@ struct ObstacleTable {
     double t0, t_ref;
     int count, pad;
     DevObstacle ob[OB_MAX];
+    double seg_radii[OB_SEGMENTS];   // capsule handles only (zeros otherwise)
 };
 // the table's room behind the 2 H step-constant slots, in StepConst units
 constexpr int OB_TABLE_STEPS = (int)((sizeof(ObstacleTable) + sizeof(StepConst) - 1) / sizeof(StepConst));

@@ -58,22 +58,28 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
-// This text is compiled as six translation units: by itself (the default mode's kernels
+// This text is compiled as eight translation units: by itself (the default mode's kernels
 // and everything the host calls), and included by fr_coop_lp.hip (FR_COOP_LP_UNIT: the kinematic
 // link-position objective), fr_coop_wr.hip (FR_COOP_WR_UNIT: the simulated end-effector wrench in
 // the step), fr_coop_wr_lp.hip (both), and fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip (FR_COOP_OB_UNIT
-// on top of LP: the obstacle term in the objective).  A variant unit holds its kernels and their
-// launchers only.
+// on top of LP: the obstacle term in the objective), and fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip
+// (FR_COOP_CAP_UNIT on top of OB: the obstacle term with segments and capsule obstacles).  A variant
+// unit holds its kernels and their launchers only.
 #if defined(FR_COOP_LP_UNIT) || defined(FR_COOP_WR_UNIT)
 #define FR_COOP_VARIANT_UNIT 1
 #endif
 #if defined(FR_COOP_OB_UNIT) && !defined(FR_COOP_LP_UNIT)
 #error "the obstacle units are link-position units"
 #endif
-#ifdef FR_COOP_OB_UNIT
-#define FR_UNIT_OB true
+#if defined(FR_COOP_CAP_UNIT) && !defined(FR_COOP_OB_UNIT)
+#error "the capsule units are obstacle units"
+#endif
+#if defined(FR_COOP_CAP_UNIT)
+#define FR_UNIT_OB OB_TERM_CAPSULES
+#elif defined(FR_COOP_OB_UNIT)
+#define FR_UNIT_OB OB_TERM_POINTS
 #else
-#define FR_UNIT_OB false
+#define FR_UNIT_OB OB_TERM_NONE
 #endif
 
 #ifdef PHASE_MARKS
@@ -1716,7 +1722,7 @@ __device__ __forceinline__ void launch_row_cost(const FrRolloutArgs &a, int64_t 
     if (frow && (a.status->all_nan || a.status->sg_error)) return;   // no filter() when the update threw
     double J;
     if constexpr (LP && FR_UNIT_OB)   // (the row's table: behind the step constants it reads)
-        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true, true>(*a.cost, frow ? a.fsteps : a.steps,
+        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true, FR_UNIT_OB>(*a.cost, frow ? a.fsteps : a.steps,
                                                                  frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H,
                                                                  lane, Lmodel + T_LO, mppi_cost::LinkModel{a.model, a.dt});
     else if constexpr (LP)
@@ -2031,7 +2037,7 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
         const bool anyf = __builtin_amdgcn_ballot_w64(frow) != 0;
         const mppi_cost::ObstacleRef ob{mppi_cost::obstacle_table_of(a.steps, a.H),
                                         anyf ? mppi_cost::obstacle_table_of(a.fsteps, a.H) : nullptr, frow, L.kk};
-        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true, FR_UNIT_OB>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
                                                                            mppi_cost::LinkModel{a.model, a.dt}, L.kk == 0, ob);
     } else if constexpr (LP)
         cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
@@ -2315,8 +2321,19 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // WR: the simulated end-effector wrench in the step (FrRolloutArgs::simulated_wrench, coop_rows),
 // again kernels and units of their own (fr_coop_wr.hip; with LP, fr_coop_wr_lp.hip).
 // OB: the obstacle term in the LP objective (FrRolloutArgs::link_positions == 2), units
-// fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip.
-#if defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
+// fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip; with segments and capsule obstacles (== 3), units
+// fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip.
+#if defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_COOP_K fr_coop_wr_lp_cap_kernel
+#define FR_COOP_XK fr_coop_x_wr_lp_cap_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR true
+#elif defined(FR_COOP_CAP_UNIT)
+#define FR_COOP_K fr_coop_lp_cap_kernel
+#define FR_COOP_XK fr_coop_x_lp_cap_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR false
+#elif defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
 #define FR_COOP_K fr_coop_wr_lp_ob_kernel
 #define FR_COOP_XK fr_coop_x_wr_lp_ob_kernel
 #define FR_UNIT_LP true
@@ -2395,6 +2412,8 @@ FR_UNIT_DECL(wr)
 FR_UNIT_DECL(wr_lp)
 FR_UNIT_DECL(lp_ob)
 FR_UNIT_DECL(wr_lp_ob)
+FR_UNIT_DECL(lp_cap)
+FR_UNIT_DECL(wr_lp_cap)
 #undef FR_UNIT_DECL
 
 template <int CK, bool EN, int WPB, bool KC>
@@ -2415,6 +2434,8 @@ template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_CAPSULES)
+        return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_cap_one(a, nb, s, WPB, KC);
     if (a.link_positions == FR_LINKS_OBSTACLES)
         return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_ob_one(a, nb, s, WPB, KC);
     if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_one(a, nb, s, WPB, KC) : launch_fr_coop_wr_one(a, nb, s, WPB, KC);
@@ -2428,6 +2449,7 @@ static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_CAPSULES) return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_x(a, nb, s) : launch_fr_coop_lp_cap_x(a, nb, s);
     if (a.link_positions == FR_LINKS_OBSTACLES) return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_x(a, nb, s) : launch_fr_coop_lp_ob_x(a, nb, s);
     if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_x(a, nb, s) : launch_fr_coop_wr_x(a, nb, s);
     if (a.link_positions) return launch_fr_coop_lp_x(a, nb, s);
@@ -2438,7 +2460,11 @@ static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 }
 
 #ifdef FR_COOP_VARIANT_UNIT
-#if defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
+#if defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_UNIT_FN(pre, post) pre##wr_lp_cap##post
+#elif defined(FR_COOP_CAP_UNIT)
+#define FR_UNIT_FN(pre, post) pre##lp_cap##post
+#elif defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
 #define FR_UNIT_FN(pre, post) pre##wr_lp_ob##post
 #elif defined(FR_COOP_OB_UNIT)
 #define FR_UNIT_FN(pre, post) pre##lp_ob##post
@@ -2495,7 +2521,7 @@ bool fr_coop_is_update_kernel(const void *f)
            f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
            f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f) ||
            fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f) || fr_coop_lp_ob_is_update_kernel(f) ||
-           fr_coop_wr_lp_ob_is_update_kernel(f);
+           fr_coop_wr_lp_ob_is_update_kernel(f) || fr_coop_lp_cap_is_update_kernel(f) || fr_coop_wr_lp_cap_is_update_kernel(f);
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at

@@ -61,6 +61,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #include "fr_step_cost_kernel_body.inc"
 }
 
+// The same with segments and capsule obstacles (FR_LINKS_CAPSULES: fr_cost_terms.hpp capsule_term)
+template <int CK, bool EN, bool KC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_cap_kernel(FrCostArgs a)
+{
+    constexpr bool LP = true;
+    constexpr int OB = OB_TERM_CAPSULES;
+#include "fr_step_cost_kernel_body.inc"
+}
+
 // An update's obstacle table from the launch's arguments into its place behind the step constants
 __global__ __launch_bounds__(64) void obstacle_table_kernel(ObstacleTable t, ObstacleTable *out)
 {
@@ -72,8 +81,10 @@ __global__ __launch_bounds__(64) void obstacle_table_kernel(ObstacleTable t, Obs
 
 // The obstacle term of the filter() row summed over its steps in step order, undiscounted, as
 // fr_terms_kernel sums the reference's seven (one wave, lane = step)
-__global__ __launch_bounds__(64) void fr_obstacle_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                               const DevModel *model, double dt, double *out1)
+// CAP: the capsule term (fr_capsule_total_kernel)
+template <bool CAP>
+__device__ __forceinline__ void obstacle_total(const StepConst *steps, const double *rec, int H, int compact,
+                                               const DevModel *model, double dt, double *out1)
 {
     const int lane = threadIdx.x;
     const ObstacleTableK T = obstacle_table_of(steps, H);
@@ -85,10 +96,22 @@ __global__ __launch_bounds__(64) void fr_obstacle_total_kernel(const StepConst *
         double qj[10], lp[SC_LINKS][3];
         for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
         link_fk(*model, qj, lp);
-        const double t = obstacle_term(T, lp, r + REC_EE, dt, k);
+        double t;
+        if constexpr (CAP) t = capsule_term(T, lp, r + REC_EE, dt, k);
+        else t = obstacle_term(T, lp, r + REC_EE, dt, k);
         for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
     }
     if (lane == 0) *out1 = tot;
+}
+__global__ __launch_bounds__(64) void fr_obstacle_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
+                                                               const DevModel *model, double dt, double *out1)
+{
+    obstacle_total<false>(steps, rec, H, compact, model, dt, out1);
+}
+__global__ __launch_bounds__(64) void fr_capsule_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
+                                                              const DevModel *model, double dt, double *out1)
+{
+    obstacle_total<true>(steps, rec, H, compact, model, dt, out1);
 }
 
 // The optimal rollout's per-term totals (AssistedManipulation's accumulators after filter(),
@@ -144,9 +167,10 @@ hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hip
 }
 
 hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                    double dt, double *out1, hipStream_t s)
+                                    double dt, double *out1, hipStream_t s, bool capsules)
 {
-    hipLaunchKernelGGL(fr_obstacle_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    if (capsules) hipLaunchKernelGGL(fr_capsule_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    else hipLaunchKernelGGL(fr_obstacle_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
     return hipGetLastError();
 }
 
@@ -156,7 +180,18 @@ hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s)
     if (rows == 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(64);
     // the records' layout is the launch's that wrote them (FrCostArgs::compact)
-    if (a.link_positions == FR_LINKS_OBSTACLES) {
+    if (a.link_positions == FR_LINKS_CAPSULES) {
+        if (!a.model) return hipErrorInvalidValue;
+        if (a.compact) {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
+        } else {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
+        }
+    } else if (a.link_positions == FR_LINKS_OBSTACLES) {
         if (!a.model) return hipErrorInvalidValue;
         if (a.compact) {
             if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);

@@ -211,6 +211,134 @@ __device__ __forceinline__ double obstacle_term(TP T, const double (*lp)[3], con
     return term;
 }
 
+// ---- capsules (mppi_set_obstacle_capsules): the links between the points, and capsule obstacles ----
+// Robot segment s joins points s and s + 1 (the pairs are compile-time indices: the link coordinates
+// stay in registers) with radius seg_radii[s], selected by mask bit 16 + s; an OB_CAPSULE obstacle is
+// the segment c -> c + normal with its radius (include/mppi_amd.h has the definition).  Everything that
+// decides a guard - A, E, B, den, t - is rounded operation by operation, as the host reference writes it.
+__device__ __forceinline__ double dot3_rn(double a0, double a1, double a2, double b0, double b1, double b2)
+{
+    return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2));
+}
+__device__ __forceinline__ double clamp01(double x)
+{
+    x = (x < 0.0) ? 0.0 : x;
+    return (x > 1.0) ? 1.0 : x;
+}
+
+// The distance between segment a -> b and segment c -> c + e, E = e . e: Ericson's closest-point form
+// with exact-zero guards only.  One straight line of selects: the clamps and the two re-solves of s
+// differ per lane.  With E = 0 the quotient by E is NaN or inf and is selected away (t = 0 and the
+// t < 0 re-solve, s = clamp(-C / A)); with A = 0, d1 = 0 makes B = C = den = 0, so s0 = 0 and t is
+// clamp(F / E), and the re-solved s (0 / 0) is selected away.
+__device__ __forceinline__ double segment_distance(const double *a, const double *b, double c0, double c1, double c2, double e0,
+                                                   double e1, double e2, double E)
+{
+    const double x0 = __dsub_rn(b[0], a[0]), x1 = __dsub_rn(b[1], a[1]), x2 = __dsub_rn(b[2], a[2]);
+    const double r0 = __dsub_rn(a[0], c0), r1 = __dsub_rn(a[1], c1), r2 = __dsub_rn(a[2], c2);
+    const double A = dot3_rn(x0, x1, x2, x0, x1, x2), F = dot3_rn(e0, e1, e2, r0, r1, r2);
+    const double Cc = dot3_rn(x0, x1, x2, r0, r1, r2), B = dot3_rn(x0, x1, x2, e0, e1, e2);
+    const double den = __dsub_rn(__dmul_rn(A, E), __dmul_rn(B, B));
+    const double sq = clamp01(__ddiv_rn(__dsub_rn(__dmul_rn(B, F), __dmul_rn(Cc, E)), den));
+    const double s0 = (den > 0.0) ? sq : 0.0;
+    const double tg = __ddiv_rn(__dadd_rn(__dmul_rn(B, s0), F), E);
+    const bool ez = E == 0.0, lo = ez || tg < 0.0, hi = !lo && tg > 1.0;
+    const double sr = clamp01(__ddiv_rn(lo ? -Cc : __dsub_rn(B, Cc), A));
+    double s = (lo || hi) ? sr : s0;
+    s = (A == 0.0) ? 0.0 : s;
+    const double t = lo ? 0.0 : (hi ? 1.0 : tg);
+    const double d0 = __dsub_rn(__dadd_rn(a[0], __dmul_rn(s, x0)), __dadd_rn(c0, __dmul_rn(t, e0)));
+    const double d1 = __dsub_rn(__dadd_rn(a[1], __dmul_rn(s, x1)), __dadd_rn(c1, __dmul_rn(t, e1)));
+    const double d2 = __dsub_rn(__dadd_rn(a[2], __dmul_rn(s, x2)), __dadd_rn(c2, __dmul_rn(t, e2)));
+    return sqrt(dot3_rn(d0, d1, d2, d0, d1, d2));
+}
+
+// The end points of robot segment s (wave-uniform), each case by name: the link coordinates stay in
+// registers, and one copy of the distance serves the eight segments
+__device__ __forceinline__ void segment_ends(const double (*lp)[3], const double *ee, int s, double *a, double *b)
+{
+#define SEG_CASE(n, P, Q) case n: for (int i = 0; i < 3; i++) { a[i] = (P)[i]; b[i] = (Q)[i]; } break;
+    switch (s) {
+        SEG_CASE(0, lp[0], lp[1]) SEG_CASE(1, lp[1], lp[2]) SEG_CASE(2, lp[2], lp[3]) SEG_CASE(3, lp[3], lp[4])
+        SEG_CASE(4, lp[4], lp[5]) SEG_CASE(5, lp[5], lp[6]) SEG_CASE(6, lp[6], lp[7])
+        default: for (int i = 0; i < 3; i++) { a[i] = lp[7][i]; b[i] = ee[i]; } break;
+    }
+#undef SEG_CASE
+}
+
+// The step's term with capsules: per obstacle, in order, the masked points in order (bits 0..8), then
+// the masked segments in order (bits 16..23), each clearance through Left(limit).  The kind and the
+// masks are the wave's: the kind branch and each segment's mask test are scalar branches (a segment
+// that no obstacle selects costs nothing), the table reads scalar loads.  A sphere is the capsule
+// with e = 0; its points' clearances are obstacle_term's, expression for expression (q = c exactly).
+// The eight segments are a rolled loop over one copy of the distance (unrolled, the x kernel, which holds
+// the objective twice, was 16 KB larger and four variants spilled where their obstacle twins did not);
+// segment_ends picks the end points by name.
+template <typename TP>
+__device__ __forceinline__ double capsule_term(TP T, const double (*lp)[3], const double *ee, double dt, int k)
+{
+    const double tau = __dsub_rn(__dadd_rn(T->t0, __dmul_rn((double)k, dt)), T->t_ref);
+    const int count = T->count;
+    const int n = count < OB_MAX ? count : OB_MAX;   // (never past the table, whatever it holds)
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    double term = 0.0;
+#pragma unroll 1
+    for (int o = 0; o < n; o++) {
+        const double c0 = __dadd_rn(T->ob[o].position[0], __dmul_rn(T->ob[o].velocity[0], tau));
+        const double c1 = __dadd_rn(T->ob[o].position[1], __dmul_rn(T->ob[o].velocity[1], tau));
+        const double c2 = __dadd_rn(T->ob[o].position[2], __dmul_rn(T->ob[o].velocity[2], tau));
+        const unsigned mask = T->ob[o].mask;
+        const int kind = T->ob[o].kind;
+        if (kind == OB_HALF_SPACE) {
+            const double n0 = T->ob[o].normal[0], n1 = T->ob[o].normal[1], n2 = T->ob[o].normal[2];
+#pragma unroll
+            for (int i = 0; i < OB_POINTS; i++) {
+                const double *p = i < SC_LINKS ? lp[i] : ee;
+                const double v = ((n0 * (p[0] - c0) + n1 * (p[1] - c1)) + n2 * (p[2] - c2)) - T->radii[i];
+                const double b = left_barrier(bound, scale, mx, v);
+                term += ((mask >> i) & 1u) ? b : 0.0;
+            }
+#pragma unroll 1
+            for (int s = 0; s < OB_SEGMENTS; s++) {
+                if ((mask >> (OB_SEGMENT_BIT0 + s)) & 1u) {
+                    double p[3], q[3];
+                    segment_ends(lp, ee, s, p, q);
+                    const double hp = (n0 * (p[0] - c0) + n1 * (p[1] - c1)) + n2 * (p[2] - c2);
+                    const double hq = (n0 * (q[0] - c0) + n1 * (q[1] - c1)) + n2 * (q[2] - c2);
+                    term += left_barrier(bound, scale, mx, ((hq < hp) ? hq : hp) - T->seg_radii[s]);
+                }
+            }
+        } else {
+            const bool cap = kind == OB_CAPSULE;
+            const double e0 = cap ? T->ob[o].normal[0] : 0.0, e1 = cap ? T->ob[o].normal[1] : 0.0, e2 = cap ? T->ob[o].normal[2] : 0.0;
+            const double E = dot3_rn(e0, e1, e2, e0, e1, e2);
+            const double ro = T->ob[o].radius;
+#pragma unroll
+            for (int i = 0; i < OB_POINTS; i++) {
+                const double *p = i < SC_LINKS ? lp[i] : ee;
+                // the point is the segment (p, p): s = 0, t = clamp(F / E), 0 with E = 0
+                const double F = dot3_rn(e0, e1, e2, __dsub_rn(p[0], c0), __dsub_rn(p[1], c1), __dsub_rn(p[2], c2));
+                const double t = (E == 0.0) ? 0.0 : clamp01(__ddiv_rn(F, E));
+                const double d0 = p[0] - __dadd_rn(c0, __dmul_rn(t, e0)), d1 = p[1] - __dadd_rn(c1, __dmul_rn(t, e1));
+                const double d2 = p[2] - __dadd_rn(c2, __dmul_rn(t, e2));
+                const double v = sqrt((d0 * d0 + d1 * d1) + d2 * d2) - (T->radii[i] + ro);
+                const double b = left_barrier(bound, scale, mx, v);
+                term += ((mask >> i) & 1u) ? b : 0.0;
+            }
+#pragma unroll 1
+            for (int s = 0; s < OB_SEGMENTS; s++) {
+                if ((mask >> (OB_SEGMENT_BIT0 + s)) & 1u) {
+                    double a[3], b[3];
+                    segment_ends(lp, ee, s, a, b);
+                    const double d = segment_distance(a, b, c0, c1, c2, e0, e1, e2, E);
+                    term += left_barrier(bound, scale, mx, d - (T->seg_radii[s] + ro));
+                }
+            }
+        }
+    }
+    return term;
+}
+
 // An update's obstacle table as the rollouts' objective reads it: nothing writes it during a launch
 // (obstacle_table_kernel ran before), so it is addressed in the constant address space, and its
 // address is made the wave's by v_readfirstlane - it is the same on every lane, but where it hangs
@@ -234,6 +362,8 @@ struct ObstacleRef {
     bool frow;
     int k;
 };
+// CAP: the capsule term (capsule_term) instead of obstacle_term
+template <bool CAP = false>
 __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt)
 {
     double term = 0.0;
@@ -241,7 +371,9 @@ __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const dou
 #pragma unroll 1
     for (int pass = 0; pass < np; pass++) {
         const ObstacleTableK T = pass ? ob.ftab : ob.tab;
-        const double t = obstacle_term(T, lp, ee, dt, ob.k);
+        double t;
+        if constexpr (CAP) t = capsule_term(T, lp, ee, dt, ob.k);
+        else t = obstacle_term(T, lp, ee, dt, ob.k);
         term = (pass == 0 || ob.frow) ? t : term;
     }
     return term;
@@ -330,8 +462,9 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 // LP: the kinematic link-position model - the self-collision term from the record's link positions
 // (lm, first: record_self_collision) instead of the zero stub's constant
 // OB (with LP): the obstacle term on the same link positions (ob: obstacle_cost), added after the
-// reference's terms; the link FK then runs whether or not the self-collision switch is on
-template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
+// reference's terms; the link FK then runs whether or not the self-collision switch is on.  OB_TERM_NONE,
+// OB_TERM_POINTS (the nine points) or OB_TERM_CAPSULES (points and segments, capsule obstacles)
+template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
                                                              const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
                                                              bool first = false, ObstacleRef ob = ObstacleRef{})
@@ -441,7 +574,7 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
         link_fk(*lm.model, qj, lp);
         double sct = 0.0;
         if (Cs.en_self) sct = self_collision_term<false>(Cs, lp);
-        const double obt = obstacle_cost(ob, lp, pe, lm.dt);
+        const double obt = obstacle_cost<OB == OB_TERM_CAPSULES>(ob, lp, pe, lm.dt);
         double cost = 0.0;
         cost += t_joint;
         cost += sct;
@@ -575,7 +708,7 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
 
 // gamma_k times the objective at step record r (AssistedManipulation: r holds the record's (q, qd)
 // pairs, the rest is read from the stored record src; TrackPoint: r holds the record up to REC_VL)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &sc, const double *r, const double *Lj,
                                            const double2 *src, LinkModel lm = LinkModel{}, bool first = false,
                                            ObstacleRef ob = ObstacleRef{})
@@ -590,14 +723,14 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
                 link_fk(*lm.model, qj, lp);
             }
             if constexpr (OB)
-                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost(ob, lp, r + REC_EE, lm.dt));
+                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost<OB == OB_TERM_CAPSULES>(ob, lp, r + REC_EE, lm.dt));
             else
                 return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
         } else {
             return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4]);
         }
     } else {
-        if constexpr (OB) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true, true>(Cs, sc, r, Lj, src, lm, first, ob);
+        if constexpr (OB) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true, OB>(Cs, sc, r, Lj, src, lm, first, ob);
         else if constexpr (LP) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
         else return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG>(Cs, sc, r, Lj, src);
     }
@@ -605,7 +738,7 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
 
 // gamma_k times the objective at the stored step record rk (FR_REC doubles, or FR_REC_C with KC;
 // 16-byte aligned)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, bool OB = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const StepConst &sc, const double *rk, const double *Lj,
                                                   LinkModel lm = LinkModel{}, bool first = false, ObstacleRef ob = ObstacleRef{})
 {
@@ -618,7 +751,7 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
         r[2 * i] = v.x;
         r[2 * i + 1] = v.y;
     }
-    if constexpr (OB) return step_cost<CK, EN, JS, KC, JG, true, true>(Cs, sc, r, Lj, src, lm, first, ob);
+    if constexpr (OB) return step_cost<CK, EN, JS, KC, JG, true, OB>(Cs, sc, r, Lj, src, lm, first, ob);
     else if constexpr (LP) return step_cost<CK, EN, JS, KC, JG, true>(Cs, sc, r, Lj, src, lm, first);
     else return step_cost<CK, EN, JS, KC, JG>(Cs, sc, r, Lj, src);
 }
@@ -629,7 +762,7 @@ __device__ __forceinline__ double record_step_cost(const DevCost &Cs, const Step
 // reference accumulates J += cost (mppi.cpp:322-337); a NaN step makes the sum NaN (the reference's
 // early stop), canonicalised to the quiet NaN it stores.  The same value on every lane.
 // OB: the obstacle term from the table behind stp (one row a wave: one table)
-template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, bool LP = false, bool OB = false>
+template <int CK, bool EN, int JS = JT_STRIDE, bool KC = false, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double rollout_cost(const DevCost &Cs, const StepConst *stp, const double *rec, int H, int lane,
                                                const double *Lj, LinkModel lm = LinkModel{})
 {
@@ -640,7 +773,7 @@ __device__ __forceinline__ double rollout_cost(const DevCost &Cs, const StepCons
         const int k = base + (lane < n ? lane : 0);
         double c;
         if constexpr (OB)
-            c = record_step_cost<CK, EN, JS, KC, 1, true, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0,
+            c = record_step_cost<CK, EN, JS, KC, 1, true, OB>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0,
                                                                 ObstacleRef{obstacle_table_of(stp, H), nullptr, false, k});
         else if constexpr (LP) c = record_step_cost<CK, EN, JS, KC, 1, true>(Cs, stp[k], rec + (int64_t)k * RS, Lj, lm, k == 0);
         else c = record_step_cost<CK, EN, JS, KC>(Cs, stp[k], rec + (int64_t)k * RS, Lj);

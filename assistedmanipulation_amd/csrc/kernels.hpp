@@ -124,7 +124,7 @@ struct FinishArgs {
 constexpr int FR_WRENCH_ROW = 8;
 static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows behind the step constants");
 // FrRolloutArgs / FrCostArgs::link_positions
-constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2;
+constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3;
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -172,6 +172,8 @@ struct FrRolloutArgs {
     // block's size and every other offset stay what the default mode's kernels were built for.
     // FR_LINKS_OBSTACLES: the model with the obstacle term as well (mppi_set_obstacle_avoidance; the
     // *_ob_kernel units), its table behind the step constants and wrench rows (steps + 2 H, fsteps + 2 H).
+    // FR_LINKS_CAPSULES: the obstacle term with segments and capsule obstacles (mppi_set_obstacle_capsules;
+    // the *_cap_kernel units), the same table with its tail of segment radii.
     int link_positions;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
@@ -515,11 +517,13 @@ hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const do
 hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hipStream_t s);
 // The obstacle term of one rollout's H records summed over its steps in step order, undiscounted
 // (next to launch_fr_terms' seven totals), from the table behind `steps`
+// (capsules: the capsule term, fr_capsule_total_kernel)
 hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                    double dt, double *out1, hipStream_t s);
+                                    double dt, double *out1, hipStream_t s, bool capsules = false);
 // mppi_dynamics_obstacle_cost: the term at the object's cached link and end-effector positions,
 // tau = t.t0 - t.t_ref
-hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
+// (capsules: mppi_dynamics_capsule_cost, fr_object_capsule_kernel)
+hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s, bool capsules = false);
 
 
 }  // namespace mppi_eng

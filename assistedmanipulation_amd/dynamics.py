@@ -186,6 +186,17 @@ class PinocchioDynamicsObject:
     def get_link_position(self, link):
         return self.link_positions()[int(link)]
 
+    def capsule_cost(self, config, capsules, obstacles, elapsed):
+        """mppi_dynamics_capsule_cost: obstacle_cost with the robot's segments (`capsules`: an
+        ObstacleCapsules or None, the defaults), capsule obstacles and segment mask bits."""
+        from .obstacles import ObstacleAvoidance, ObstacleCapsules, obstacles_to_c
+        c = (config or ObstacleAvoidance()).to_c()
+        cc = (capsules or ObstacleCapsules()).to_c()
+        arr, n = obstacles_to_c(obstacles)
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_dynamics_capsule_cost(self._h, C.byref(c), C.byref(cc), arr, n, float(elapsed), C.byref(v)))
+        return v.value
+
     def obstacle_cost(self, config, obstacles, elapsed):
         """mppi_dynamics_obstacle_cost: the obstacle term (Trajectory.set_obstacle_avoidance) of
         `obstacles` moved by `elapsed` seconds, at the link and end-effector positions the object

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import abi
 from ._lib import load
-from .obstacles import ObstacleAvoidance, obstacle_from_c, obstacles_to_c
+from .obstacles import ObstacleAvoidance, ObstacleCapsules, obstacle_from_c, obstacles_to_c
 from .config import Configuration
 from .safety import TrajectorySafetyFilter
 
@@ -371,6 +371,20 @@ class Trajectory:
         on, c = C.c_int(0), abi.mppi_obstacle_config()
         self._check(self._L.mppi_get_obstacle_avoidance(self._h, C.byref(on), C.byref(c)))
         return ObstacleAvoidance.from_c(c) if on.value else None
+
+    def set_obstacle_capsules(self, capsules=None):
+        """mppi_set_obstacle_capsules: the robot's eight segments (the links between consecutive robot
+        points) and capsule obstacles in the obstacle term, with `capsules` (an ObstacleCapsules; None:
+        the defaults).  After set_obstacle_avoidance and before the first update; it cannot be undone."""
+        c = (capsules or ObstacleCapsules()).to_c()
+        self._check(self._L.mppi_set_obstacle_capsules(self._h, C.byref(c)))
+
+    @property
+    def obstacle_capsules(self):
+        """The ObstacleCapsules configuration the handle runs with, or None without capsules."""
+        on, c = C.c_int(0), abi.mppi_capsule_config()
+        self._check(self._L.mppi_get_obstacle_capsules(self._h, C.byref(on), C.byref(c)))
+        return ObstacleCapsules.from_c(c) if on.value else None
 
     def set_obstacles(self, obstacles, time):
         """mppi_set_obstacles: replace the whole set (SphereObstacle / HalfSpaceObstacle, at most 16;

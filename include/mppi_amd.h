@@ -437,12 +437,51 @@ mppi_status mppi_get_simulated_wrench(mppi_handle *h, int *mode);
  * steps, undiscounted, next to mppi_optimal_terms' seven totals (which, like mppi_cost_evaluate,
  * keep their terms and totals as they are); waits for (or runs) that filter() the same way; 0 with
  * an empty set or before the first published update, MPPI_ERR_UNSUPPORTED when avoidance is off.
- * Added after ABI version 5 without a version change (new structs only): detect by symbol. */
+ * Added after ABI version 5 without a version change (new structs only): detect by symbol.
+ *
+ * Capsules (mppi_set_obstacle_capsules): the links between the robot's points, and capsule obstacles.
+ * Robot segment s (s = 0..MPPI_OBSTACLE_SEGMENTS - 1) joins robot point s and robot point s + 1, with
+ * the points' lag (q_0 for k = 0, q_{k-1} after) and its own radius segment_radii[s]; the pairs are
+ * fixed.  Segments 1 and 5 have zero length on this robot (joints 1 and 2, and 5 and 6, coincide):
+ * they are legal and behave as points.  Bits 0..8 of a mask keep their meaning; bit 16 + s selects
+ * segment s (MPPI_OBSTACLE_MASK_SEGMENT(s), all of them MPPI_OBSTACLE_MASK_SEGMENTS).
+ * MPPI_OBSTACLE_MASK_ALL stays the nine points: a set written for a handle without capsules means
+ * on a capsule handle exactly what it meant.  MPPI_OBSTACLE_CAPSULE is the segment from c_o(k) to
+ * c_o(k) + normal with radius >= 0: the normal field is the axis vector, any finite vector (zero: a
+ * sphere), and the whole capsule translates with velocity.
+ * The distance d(a, b; c, e) between segment a -> b and segment c -> c + e is Ericson's closest-point
+ * form with exact-zero guards only.  d1 = b - a, r = a - c, A = d1 . d1, E = e . e, F = e . r:
+ *   A = 0 and E = 0: s = t = 0.    A = 0, E != 0: s = 0, t = clamp01(F / E).
+ *   otherwise C = d1 . r;  E = 0: t = 0, s = clamp01(-C / A);  else B = d1 . e, den = A E - B B,
+ *     s = clamp01((B F - C E) / den) if den > 0 else 0,  t = (B s + F) / E,
+ *     t < 0: t = 0, s = clamp01(-C / A);   t > 1: t = 1, s = clamp01((B - C) / A)
+ *   d = |(a + s d1) - (c + t e)|
+ * every operation rounded by itself.  A robot point is the segment (p, p), a sphere the capsule e = 0.
+ * Clearance:
+ *   point i,   sphere / half-space   as above
+ *   point i,   capsule               v = d(p_i, p_i; c, e) - (radii[i] + radius_o)
+ *   segment s, sphere or capsule     v = d(p_s, p_{s+1}; c, e) - (segment_radii[s] + radius_o)
+ *   segment s, half-space            v = min(n . (p_s - c), n . (p_{s+1} - c)) - segment_radii[s]
+ * and the step's term is, per obstacle in index order, the masked points in index order, then the
+ * masked segments in index order, each through Left(limit); it is added where the obstacle term is.
+ * mppi_set_obstacle_capsules (config NULL: mppi_default_capsule_config, 0.1 for every segment) selects
+ * the capsule kernels for the handle's life: after mppi_set_obstacle_avoidance and before the first
+ * update (MPPI_ERR_INVALID otherwise, the message says which), radii finite and >= 0.
+ * mppi_get_obstacle_capsules: enabled = 0 for a handle that never enabled them (out untouched).
+ * mppi_set_obstacles on a handle without capsules refuses the capsule kind and any mask bit above 8;
+ * on a capsule handle bits 0..8 and 16..23 are legal, every other bit is invalid, and a capsule's
+ * axis must be finite (it need not be a unit vector; a half-space normal still must).
+ * mppi_optimal_obstacle_cost returns the capsule term's total on a capsule handle.
+ * Added like the obstacle symbols, without a version change: detect by symbol. */
 #define MPPI_MAX_OBSTACLES 16
 #define MPPI_OBSTACLE_POINTS 9
 #define MPPI_OBSTACLE_SPHERE 0
 #define MPPI_OBSTACLE_HALF_SPACE 1
+#define MPPI_OBSTACLE_CAPSULE 2
 #define MPPI_OBSTACLE_MASK_ALL 0x1FFu
+#define MPPI_OBSTACLE_SEGMENTS 8
+#define MPPI_OBSTACLE_MASK_SEGMENT(s) (1u << (16 + (s)))
+#define MPPI_OBSTACLE_MASK_SEGMENTS 0xFF0000u
 typedef struct mppi_obstacle {
     int32_t kind;     /* MPPI_OBSTACLE_* */
     uint32_t mask;    /* bit i: robot point i is tested */
@@ -458,6 +497,12 @@ mppi_status mppi_get_obstacle_avoidance(mppi_handle *h, int *enabled, mppi_obsta
 mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, int32_t count, double time);
 mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *count, double *time);
 mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost);
+typedef struct mppi_capsule_config {
+    double segment_radii[MPPI_OBSTACLE_SEGMENTS];
+} mppi_capsule_config;
+void mppi_default_capsule_config(mppi_capsule_config *out);
+mppi_status mppi_set_obstacle_capsules(mppi_handle *h, const mppi_capsule_config *config);
+mppi_status mppi_get_obstacle_capsules(mppi_handle *h, int *enabled, mppi_capsule_config *out);
 
 /* The trajectory safety filter: FrankaRidgeback::TrajectorySafetyFilter::Configuration
  * (frankaridgeback/safety.hpp:15-40) field for field.  The reference declares the class and leaves
@@ -727,6 +772,10 @@ mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out);
  * MPPI_ERR_INVALID unless the object is in MPPI_LINK_POSITIONS_KINEMATIC. */
 mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
                                         const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost);
+/* The same with capsules (mppi_set_obstacle_capsules above): the robot's segments with `capsules`' radii
+ * (NULL: the defaults), capsule obstacles and segment mask bits legal. */
+mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_capsule_config *capsules,
+                                       const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost);
 /* add_end_effector_simulated_wrench (6 doubles: force, moment; semantics above): cumulative; the
  * next mppi_dynamics_step applies the sum and zeroes it.  get_end_effector_simulated_wrench: the
  * wrench the last step applied, zeros before any step. */

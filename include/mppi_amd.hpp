@@ -303,6 +303,21 @@ public:
         int on = 0;
         return mppi_get_obstacle_avoidance(m_h, &on, out) == MPPI_OK && on != 0;
     }
+    // Capsules (mppi_set_obstacle_capsules; nullptr: the default radii): the robot's eight segments and
+    // capsule obstacles in the obstacle term.  After set_obstacle_avoidance, before the first update;
+    // false and a message on stderr otherwise.
+    bool set_obstacle_capsules(const mppi_capsule_config *config = nullptr)
+    {
+        if (mppi_set_obstacle_capsules(m_h, config) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // whether they are on, and the radii the handle runs with
+    bool obstacle_capsules(mppi_capsule_config *out = nullptr) const
+    {
+        int on = 0;
+        return mppi_get_obstacle_capsules(m_h, &on, out) == MPPI_OK && on != 0;
+    }
     // the whole set, given at reference time `time` (mppi_set_obstacles): between any two updates
     bool set_obstacles(const std::vector<mppi_obstacle> &obstacles, double time)
     {
@@ -623,6 +638,14 @@ public:
     {
         double c = 0.0;
         check(mppi_dynamics_obstacle_cost(object(), config, obstacles.data(), (int32_t)obstacles.size(), elapsed, &c));
+        return c;
+    }
+    // the same with the robot's segments, capsule obstacles and segment mask bits (mppi_dynamics_capsule_cost)
+    double capsule_cost(const std::vector<mppi_obstacle> &obstacles, double elapsed, const mppi_obstacle_config *config = nullptr,
+                        const mppi_capsule_config *capsules = nullptr)
+    {
+        double c = 0.0;
+        check(mppi_dynamics_capsule_cost(object(), config, capsules, obstacles.data(), (int32_t)obstacles.size(), elapsed, &c));
         return c;
     }
     std::vector<double> get_joint_position() { return query(0, 12); }

@@ -1,0 +1,489 @@
+"""Obstacle avoidance with capsules (mppi_set_obstacle_capsules) on the device against the numpy
+composition of capsule_reference.py: the capsule term in every launch plan of the rollouts, both
+objectives, the tank, the simulated wrench, the separate cost kernel, the graph path, sharding, the
+device object (every (s, t) class of the segment-segment distance, and a near-parallel pair), point-only
+sets on a capsule handle, the refusals and the C++ surface.
+
+The pattern is test_gpu_obstacles.py's: three updates at time 0 from test_gpu_link_positions.py's three
+states with its noise scaling, host-injected noise, helpers.py's bars.  The set changes between the
+updates (capsule_sets.py): "clear" (C), "breach" (D), then empty.  The reference keeps books on every
+clearance it evaluates, and each run asserts from them that nothing sat within 1e-6 of the barrier's
+branch discontinuity, that set C stayed 0.02 m clear, and that set D's obstacles took both branches
+(the sphere inside the forearm at every shape; the flying bar and the zero-axis capsule on the grasp
+frame need a horizon of 33 steps to be reached and to be left).
+"""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import assistedmanipulation_amd as am
+from assistedmanipulation_amd import abi
+
+import capsule_reference as CR
+import capsule_sets as CS
+import link_reference as LR
+import obstacle_reference as OR
+import obstacle_sets as SETS
+import wrench_reference as WR
+from launch_shapes import by_name, horizon
+from test_gpu_link_positions import SHAPES, _assert_bars, _hip, _noise_scale, _record, _states
+from test_gpu_obstacles import MARGIN, _close, _invalid, _set_env
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLEAR_C = 0.02     # least v of set C
+BOTH = {"inverse", "saturated"}
+
+
+def _check_books(term, j, H, tag):
+    """The guards on the reference's own bookkeeping for the sets of capsule_sets.cde()."""
+    if not term.obstacles:
+        assert term.evaluated == 0
+        return
+    assert term.least_margin >= MARGIN, (tag, j, term.least_margin)
+    if j == 0:
+        assert term.least_v >= CLEAR_C and all(b == {"inverse"} for b in term.branches), (tag, term.least_v, term.branches)
+    if j == 1:
+        assert term.branches[0] == BOTH, (tag, term.branches)
+        if H >= 33:
+            assert term.branches[1] == BOTH and term.branches[2] == BOTH, (tag, term.branches)
+
+
+def _handle(conf, cost, config=None, capsules=None, wrench=None, enable=True):
+    dyn = am.FrankaRidgebackDynamics(link_positions=True, simulated_wrench=wrench)
+    dev = am.Trajectory.create(conf, dyn, cost)
+    assert dev is not None and dev.link_positions
+    dev.set_obstacle_avoidance(config)
+    if enable:
+        assert dev.obstacle_capsules is None
+        dev.set_obstacle_capsules(capsules)
+        assert dev.obstacle_capsules == (capsules or am.ObstacleCapsules())
+    dev.set_noise_source(abi.MPPI_NOISE_HOST_INJECTED)
+    return dyn, dev
+
+
+def _run(name, cost, sets, monkeypatch, plans=True, comp=None, books=True):
+    """test_gpu_obstacles.py::_run on a capsule handle.  comp: the composition to compare against (the
+    capsule reference unless given)."""
+    _, S, H, keep, req, sw, first, pend = by_name(name)
+    _set_env(monkeypatch, req, sw)
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    table = am.constant_forecast(H)
+    dyn, dev = _handle(conf, cost, capsules=CS.capsules())
+    assert dev.H == H and dev.R == S + 2
+    dev.set_forecast(table)
+    comp = comp(conf, dyn.model, cost, table) if comp else CR.Composition(conf, dyn.model, cost, table, capsules=CS.capsules())
+    states, scale = _states(), _noise_scale(H)
+    rng = np.random.default_rng(11)
+    sd = np.sqrt(np.diag(conf.covariance)) * scale
+    U = np.zeros((H, dev.C))
+    prev = None
+    for j, (x, (obstacles, t_ref)) in enumerate(zip(states, sets)):
+        tag = "%s upd %d" % (name, j)
+        dev.set_obstacles(obstacles, t_ref)
+        got_set, got_time = dev.obstacles()
+        assert [type(o) for o in got_set] == [type(o) for o in obstacles] and got_time == t_ref
+        term = comp.set_obstacles(obstacles, t_ref)
+        dev.inject_noise(rng.standard_normal((dev.noise_draws(0.0), dev.C)) * sd)
+        dev.update(x, 0.0)
+        info = dev.update_info()
+        assert info["wait_timeouts"] == 0 and info["cooperative"] == 1, (tag, info)
+        if plans:
+            want = first if j == 0 else pend
+            assert info["folded_filter"] == want[5] and info["objective_in_launch"] == want[6], (tag, info)
+        if info["folded_filter"]:   # the previous update's filter() row: its own set, before any optimal-cost read
+            comp.term = prev
+            ref = comp.rollout(states[j - 1], U)[0]
+            comp.term = term
+            _close(dev.debug_folded_cost(), ref, tag + " folded filter()")
+        eps = dev.noise()
+        J = comp.costs(x, U, eps)
+        w, g, Un = LR.mppi_update(conf, J, eps, U)
+        _assert_bars(tag, dev.costs(), J, dev.get_weights(), w, dev.get_optimal_rollout(), Un, H)
+        U = dev.get_optimal_rollout()
+        if books:
+            print("%s books: least margin %.3e, least v %.4f, %s" % (tag, term.least_margin, term.least_v, term.branches))
+            _check_books(term, j, H, tag)
+        if not plans:
+            ref, _, ob = comp.rollout(x, U)
+            _close(dev.get_optimal_obstacle_cost(), ob.sum(), tag + " optimal capsule cost")
+            _close(dev.get_optimal_total_cost(), ref, tag + " optimal total")
+        prev = term
+    ref, sc, ob = comp.rollout(states[len(sets) - 1], U)
+    _close(dev.get_optimal_total_cost(), ref, name + " optimal total")
+    _close(dev.get_optimal_obstacle_cost(), ob.sum(), name + " optimal capsule cost")
+    if cost.descriptor().kind == abi.MPPI_COST_ASSISTED_MANIPULATION:
+        _close(dev.get_optimal_terms()[1], sc.sum(), name + " self-collision total")
+    return dev, comp
+
+
+# ---- 1. parity against the composition, every launch plan ---------------------------------------
+
+@pytest.mark.parametrize("name", SHAPES)
+def test_update_against_the_composition(name, monkeypatch):
+    _run(name, CS.objective(), CS.cde(), monkeypatch)
+
+
+def test_optimal_capsule_cost_after_every_update(monkeypatch):
+    """The optimal rollout read after each update (filter() runs by itself): the capsule total of the
+    non-empty sets against the reference's sum, and the bar's segment tests span classes."""
+    dev, comp = _run("r19_h33", CS.objective(), CS.cde(), monkeypatch, plans=False)
+    assert [len(t.obstacles) for t in comp.history] == [4, 3, 0]
+    assert len(comp.history[1].classes[1] & set(CR.PROPER)) >= 2, comp.history[1].classes
+
+
+# ---- 2. other objectives and modes --------------------------------------------------------------
+
+def test_track_point(monkeypatch):
+    _run("r19_h33", CS.objective("track_point"), CS.cde(), monkeypatch)
+
+
+def test_energy_tank(monkeypatch):
+    _run("r19_h33", CS.objective(energy=True), CS.cde(), monkeypatch)
+
+
+def test_simulated_wrench_forecast(monkeypatch):
+    """The pushed robot with the capsule term: test_gpu_obstacles.py's wrench test on a capsule handle."""
+    from test_gpu_simulated_wrench import TIMES, _assert_update, _state
+    _, S, H, keep, req, sw, _, _ = by_name("r19_h33")
+    _set_env(monkeypatch, req, sw)
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    cost = CS.objective()
+    table = WR.forecast_table(H)
+    dyn, dev = _handle(conf, cost, capsules=CS.capsules(), wrench="forecast")
+    dev.set_forecast(table)
+    ref = CR.WrenchComposition(conf, dyn.model, cost, "forecast", table, capsules=CS.capsules())
+    sd = np.sqrt(np.diag(conf.covariance))
+    rng, shift, dt = np.random.default_rng(11), WR.Shift(), dev.get_time_step()
+    prev = None
+    for j, (t, (obstacles, t_ref)) in enumerate(zip(TIMES, CS.cde())):
+        tag = "wrench upd %d" % j
+        x0 = _state(j)
+        U_prev = dev.get_optimal_rollout()
+        U_shift = WR.shifted(U_prev, shift(t, dt))
+        dev.set_obstacles(obstacles, t_ref)
+        term = ref.set_obstacles(obstacles, t_ref)
+        dev.inject_noise(rng.standard_normal((dev.noise_draws(t), 12)) * sd)
+        dev.update(x0, t)
+        info = dev.update_info()
+        assert info["wait_timeouts"] == 0, (tag, info)
+        if info["folded_filter"]:
+            ref.term = prev[0]
+            want = ref.rollout(prev[1], U_prev, prev[2])[0]
+            ref.term = term
+            _close(dev.debug_folded_cost(), want, tag + " folded filter()")
+        eps = dev.noise()
+        J = ref.costs(x0, U_shift, eps, t)
+        w, g, Un = LR.mppi_update(conf, J, eps, U_shift)
+        _assert_update(tag, dev, J, w, g, Un, H)
+        if term.obstacles:
+            assert term.least_margin >= MARGIN, (tag, term.least_margin)
+        prev = (term, x0, t)
+    want, _, ob = ref.rollout(x0, dev.get_optimal_rollout(), TIMES[-1])
+    _close(dev.get_optimal_total_cost(), want, "wrench optimal total")
+    _close(dev.get_optimal_obstacle_cost(), ob.sum(), "wrench optimal capsule cost")
+
+
+def test_point_only_sets_on_a_capsule_handle(monkeypatch):
+    """Sets A and B of the obstacle tests, with their point-only masks, given to a capsule handle mean
+    what they meant: obstacle_reference.Composition, unchanged, at the bars."""
+    sets = [(SETS.set_a(), SETS.T_REF_A), (SETS.set_b(), 0.0), ([], 0.0)]
+    _run("r19_h33", SETS.objective(), sets, monkeypatch, plans=False, comp=OR.Composition, books=False)
+
+
+# ---- 3. paths ------------------------------------------------------------------------------------
+
+def test_in_launch_objective_against_the_cost_kernel(monkeypatch):
+    """The same inputs through the launch's own objective and through fr_step_cost_cap_kernel
+    (MPPI_COSTS_IN_LAUNCH=0), r147_h64, test_gpu_obstacles.py's structure: bit for bit (the two inline
+    the same text of the term, and the capsule term's arithmetic is rounded operation by operation)."""
+    _, S, H, keep, req, sw, _, _ = by_name("r147_h64")
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    cost = CS.objective()
+    _set_env(monkeypatch, req, "")
+    a = _handle(conf, cost, capsules=CS.capsules())[1]
+    _set_env(monkeypatch, req, "c")
+    b = _handle(conf, cost, capsules=CS.capsules())[1]
+    rng = np.random.default_rng(4)
+    sd = np.sqrt(np.diag(conf.covariance)) * _noise_scale(H)
+    same = True
+    for j, (x, (obstacles, t_ref)) in enumerate(zip(_states(), CS.cde())):
+        eps = rng.standard_normal((a.noise_draws(0.0), a.C)) * sd
+        for t in (a, b):
+            t.set_forecast(am.constant_forecast(H))
+            t.set_obstacles(obstacles, t_ref)
+            t.inject_noise(eps)
+            t.update(x, 0.0)
+            assert t.update_info()["wait_timeouts"] == 0
+        assert a.update_info()["objective_in_launch"] == 1 and b.update_info()["objective_in_launch"] == 0
+        same = same and np.array_equal(a.costs(), b.costs()) and np.array_equal(a.get_optimal_rollout(), b.get_optimal_rollout())
+        _assert_bars("in-launch vs cost kernel upd %d" % j, a.costs(), b.costs(), a.get_weights(), b.get_weights(),
+                     a.get_optimal_rollout(), b.get_optimal_rollout(), H)
+    assert same, "the in-launch capsule objective and the cost kernel differ in some bit"
+
+
+def _philox(conf, graph=0):
+    t = am.Trajectory.create(conf, am.FrankaRidgebackDynamics(link_positions=True), am.AssistedManipulation())
+    assert t is not None
+    t.set_obstacle_avoidance()
+    t.set_obstacle_capsules(CS.capsules())
+    t.set_graph(graph)
+    t.set_noise_source(abi.MPPI_NOISE_DEVICE_PHILOX, seed=0x5EED)
+    t.set_forecast(am.constant_forecast(t.H))
+    return t
+
+
+GRAPH_SETS = [(CS.set_c(), CS.T_REF_C), (CS.set_d(), 0.0), (CS.set_c()[:2], 0.06), (CS.set_d(), 0.1)]
+
+
+def test_graph_path(monkeypatch):
+    """test_gpu_obstacles.py::test_graph_path on a capsule handle: the set replaced and the time advancing
+    between the replays, the graph's rollout nodes give the eager launches' bits."""
+    _set_env(monkeypatch, 0, "")
+    conf = am.frankaridgeback_configuration(rollouts=1000, horison=0.64, keep_best_rollouts=20, threads=8)
+    out = {}
+    for graph in (0, 1):
+        t = _philox(conf, graph)
+        x = am.huddled_state()
+        rec = []
+        for j, tm in enumerate([0.0, 0.05, 0.07, 0.12]):
+            if j == 2:
+                x = x.copy()
+                x[12 + 4] = 0.3
+            t.set_obstacles(*GRAPH_SETS[j])
+            t.update(x, tm)
+            assert t.update_info()["wait_timeouts"] == 0
+            rec.append(_record(t))
+        out[graph] = (rec, t.graph_updates(), t.get_optimal_total_cost(), t.get_optimal_obstacle_cost())
+    assert out[0][1] == 0 and out[1][1] == 3, (out[0][1], out[1][1])
+    assert out[0][2] == out[1][2] and out[0][3] == out[1][3] and out[0][3] > 0.0
+    for j, (a, b) in enumerate(zip(out[0][0], out[1][0])):
+        for what, u, v in zip(("noise", "costs", "optimal", "weights"), a, b):
+            np.testing.assert_array_equal(u, v, err_msg="update %d %s" % (j, what))
+    # the segments are live: the same sets with their segment bits cleared give other costs
+    points = _philox(conf, 0)
+    points.set_obstacles([am.CapsuleObstacle(o.position, o.normal, o.radius, o.velocity, o.mask & am.MASK_ALL) if
+                          isinstance(o, am.CapsuleObstacle) else o for o in GRAPH_SETS[0][0]], GRAPH_SETS[0][1])
+    points.update(am.huddled_state(), 0.0)
+    assert not np.array_equal(points.costs(), out[0][0][0][1])
+
+
+def test_two_shards_equal_one_handle(monkeypatch):
+    """Two phase-split shards against one handle at 128 x 32, every rank with the same capsules and set:
+    test_gpu_obstacles.py's structure and bars."""
+    _set_env(monkeypatch, 0, "")
+    conf = am.frankaridgeback_configuration(rollouts=128, horison=horizon(32), keep_best_rollouts=20, threads=8)
+    world = 2
+    single, shards = _philox(conf), [_philox(conf) for _ in range(world)]
+    assert single.H == 32
+    for r, sh in enumerate(shards):
+        sh.set_shard(world, r)
+    hip = _hip()
+    R, HC = single.R, single.H * single.C
+    x = am.huddled_state()
+
+    def allreduce(ptrs, n):
+        bufs = [np.zeros(n) for _ in ptrs]
+        for p, b in zip(ptrs, bufs):
+            assert hip.hipMemcpy(b.ctypes.data, p, n * 8, 2) == 0   # D2H
+        s = bufs[0].copy()
+        for b in bufs[1:]:
+            s += b
+        for p in ptrs:
+            assert hip.hipMemcpy(p, s.ctypes.data, n * 8, 1) == 0   # H2D
+
+    for j in range(3):
+        t = 0.05 * j
+        for h in [single] + shards:
+            h.set_obstacles(*GRAPH_SETS[j])
+        single.update(x, t)
+        for sh in shards:
+            sh.update_phase1(x, t)
+        hip.hipDeviceSynchronize()
+        allreduce([sh.device_costs_ptr() for sh in shards], R + 1)   # + slot R: wait timeouts
+        for sh in shards:
+            sh.update_phase2()
+        hip.hipDeviceSynchronize()
+        allreduce([sh.device_gradient_ptr() for sh in shards], HC)
+        for sh in shards:
+            sh.update_phase3(t)
+        cu = single.costs()
+        delta = np.nanmax(cu) - np.nanmin(cu)
+        assert single.update_info()["wait_timeouts"] == 0
+        for sh in shards:
+            cs = sh.costs()
+            if j == 0:
+                np.testing.assert_array_equal(cs, cu)
+            assert np.all(np.abs(cs - cu) <= 1e-11 * (delta + np.abs(cu)))
+            assert np.max(np.abs(sh.get_optimal_rollout() - single.get_optimal_rollout())) <= 1e-12
+            assert np.max(np.abs(sh.get_weights() - single.get_weights())) <= 3e-15
+            assert sh.argmin() == single.argmin() and sh.update_info()["wait_timeouts"] == 0
+
+
+# ---- 4. the device object ------------------------------------------------------------------------
+
+# test_capsules_cpu.py's hand cases of the proper classes (robot segment (0,0,0) -> (4,0,0)), one a class,
+# and the crossing pair: c, e
+CLASS_CASES = [((-3.0, 4.0, 0.0), (-1.0, 1.0, 0.0)), ((-3.0, -1.0, 0.0), (0.0, 2.0, 0.0)), ((-3.0, -6.0, 0.0), (0.0, 2.0, 0.0)),
+               ((2.0, 1.0, 0.0), (0.0, 1.0, 0.0)), ((2.0, -1.0, 1.0), (0.0, 2.0, 0.0)), ((2.0, -3.0, 0.0), (0.0, 2.0, 0.0)),
+               ((7.0, 4.0, 0.0), (1.0, 1.0, 0.0)), ((7.0, -1.0, 0.0), (0.0, 2.0, 0.0)), ((7.0, -6.0, 0.0), (0.0, 2.0, 0.0)),
+               ((2.0, -1.0, 0.0), (0.0, 2.0, 0.0))]
+
+
+def _segment_frame(p, s):
+    """Segment s of the points p as a frame: its start, and u (along it), w, v scaled to a quarter of
+    its length, so that the hand cases' coordinates map onto it."""
+    a, d = p[s], p[s + 1] - p[s]
+    k = np.linalg.norm(d) / 4.0
+    u = d / np.linalg.norm(d)
+    w = np.cross(u, [0.0, 0.0, 1.0])
+    w /= np.linalg.norm(w)
+    return a, k * u, k * w, k * np.cross(u, w)
+
+
+def _class_set(p):
+    """Obstacles around segment 4 (the forearm) of the points p whose tests end in each of the nine
+    proper classes, a crossing bar, and the three degenerate entries on segments 1, 4 and 5."""
+    a, u, w, v = _segment_frame(p, 4)
+    on = lambda x: x[0] * u + x[1] * w + x[2] * v   # noqa: E731
+    out = [am.CapsuleObstacle(a + on(c), on(e), 0.01, mask=am.mask_segment(4)) for c, e in CLASS_CASES]
+    out.append(am.SphereObstacle(a + on((1.0, 0.0, 3.0)), 0.02, mask=am.mask_segment(4) | am.mask_segment(1)))     # E=0; A=0 E=0
+    out.append(am.CapsuleObstacle(a + on((6.0, 3.0, 0.0)), on((0.0, -2.0, 1.0)), 0.02, mask=am.mask_segment(5) | (1 << 5)))   # A=0
+    return out
+
+
+def test_device_object_capsule_cost(monkeypatch):
+    """PinocchioDynamicsObject.capsule_cost at huddled_state() against the numpy term, 1e-12 relative,
+    set by set and obstacle by obstacle (a saturated obstacle's 1e10 hides the others in a sum): the
+    tests' sets, and obstacles built from the numpy robot points so that the reference's books show all
+    nine (s, t) classes and the three degenerate entries.
+
+    The near-parallel obstacle: its axis is the numpy direction of segment 4, so den = A E - B B is
+    rounding noise of either sign, on the device as in numpy, and s is then anything in [0, 1]; the
+    distance is the closest pair's all the same (t follows s, and the segments overlap), and it meets
+    the same 1e-12.  The measured error relative to the clearance is printed (DESIGN section 2 has it)."""
+    monkeypatch.delenv("MPPI_LINK_POSITIONS", raising=False)
+    model = am.FrankaRidgebackDynamics().model
+    x = am.huddled_state()
+    p = OR.robot_points(model, x[:12])
+    obj = am.PinocchioDynamicsObject.create(x, link_positions=True)
+    obj.set_state(x, 0.0)
+    config = am.ObstacleAvoidance(limit=(0.01, 2.0, 1e8), radii=(0.7, 0.11, 0.12, 0.13, 0.1, 0.09, 0.08, 0.07, 0.06))
+    caps = am.ObstacleCapsules((0.1, 0.05, 0.06, 0.07, 0.04, 0.05, 0.06, 0.03))
+    classes = _class_set(p)
+    cases = [(None, CS.capsules(), CS.set_c(), 0.07), (None, CS.capsules(), CS.set_d(), 0.0), (None, CS.capsules(), CS.set_d(), 0.3),
+             (config, caps, CS.set_d() + CS.set_c(), 0.25), (None, None, SETS.set_a(), 0.07), (config, caps, SETS.set_16(), 0.5),
+             (None, caps, classes, 0.0), (None, None, [], 1.0)]
+    seen = set()
+    for conf, cc, obstacles, elapsed in cases:
+        for sub in [obstacles] + [[o] for o in obstacles]:
+            term = CR.Term(conf or am.ObstacleAvoidance(), cc or am.ObstacleCapsules(), sub, 0.0)
+            want = term.at(p, elapsed)
+            got = obj.capsule_cost(conf, cc, sub, elapsed)
+            assert abs(got - want) <= 1e-12 * max(abs(want), 1.0), (len(obstacles), len(sub), elapsed, got, want)
+            if sub is classes:
+                assert term.least_margin >= MARGIN
+                seen = set().union(*term.classes)
+    assert seen == set(CR.PROPER) | set(CR.DEGENERATE), sorted(seen)
+    # near-parallel: a bar beside the forearm, along it
+    a, u, w, v = _segment_frame(p, 4)
+    d = p[5] - p[4]
+    for start, scale in ((a + u + 0.1 * w / np.linalg.norm(w), 0.5), (a - 2 * u + 0.08 * v / np.linalg.norm(v), 2.0)):
+        bar = am.CapsuleObstacle(start, scale * d, 0.01, mask=am.mask_segment(4))
+        term = CR.Term(am.ObstacleAvoidance(), caps, [bar], 0.0)
+        want = term.at(p, 0.0)
+        got = obj.capsule_cost(None, caps, [bar], 0.0)
+        print("near-parallel bar: clearance %.6f, term %.17g against %.17g, error relative to the clearance %.3e, classes %s"
+              % (term.least_v, got, want, abs(1.0 / got - 1.0 / want) / term.least_v, sorted(term.classes[0])))
+        assert term.branches == [{"inverse"}] and abs(got - want) <= 1e-12 * max(abs(want), 1.0), (got, want)
+    # the obstacle cost is what it was, and refuses what a handle without capsules refuses
+    assert obj.obstacle_cost(None, SETS.set_a(), 0.07) == obj.capsule_cost(None, None, SETS.set_a(), 0.07)
+    _invalid(lambda: obj.obstacle_cost(None, CS.set_c(), 0.0), word="capsule")
+    _invalid(lambda: obj.capsule_cost(None, am.ObstacleCapsules((0.1,) * 7 + (-0.1,)), [], 0.0), word="segment_radii")
+    zero = am.PinocchioDynamicsObject.create(x)
+    _invalid(lambda: zero.capsule_cost(None, None, CS.set_c(), 0.0), word="kinematic")
+
+
+# ---- 5. validation -------------------------------------------------------------------------------
+
+def test_validation(monkeypatch):
+    _set_env(monkeypatch)
+    conf = am.frankaridgeback_configuration(rollouts=17, horison=0.05, keep_best_rollouts=5)
+    mk = lambda: am.Trajectory.create(conf, am.FrankaRidgebackDynamics(link_positions=True), am.AssistedManipulation())   # noqa: E731
+    post = am.CapsuleObstacle((2, 2, 0), (0, 0, 2), 0.05)
+    ball = am.SphereObstacle((2, 2, 1), 0.1)
+
+    # before avoidance is enabled, and after the first update
+    t = mk()
+    assert t.obstacle_capsules is None
+    _invalid(lambda: t.set_obstacle_capsules(), word="not enabled")
+    t.set_obstacle_avoidance()
+    assert t.obstacle_capsules is None
+    # a handle without capsules: the capsule kind and the segment bits stay invalid
+    _invalid(lambda: t.set_obstacles([post], 0.0), word="capsule")
+    _invalid(lambda: t.set_obstacles([am.SphereObstacle((2, 2, 1), 0.1, mask=am.mask_segment(0))], 0.0), word="mask")
+    _invalid(lambda: t.set_obstacles([am.SphereObstacle((2, 2, 1), 0.1, mask=am.MASK_ALL | am.MASK_SEGMENTS)], 0.0), word="mask")
+    # the radii
+    for bad in (am.ObstacleCapsules((0.1,) * 7 + (-0.01,)), am.ObstacleCapsules((np.nan,) + (0.1,) * 7),
+                am.ObstacleCapsules((0.1, np.inf) + (0.1,) * 6)):
+        _invalid(lambda: t.set_obstacle_capsules(bad), word="segment_radii")
+        assert t.obstacle_capsules is None
+    t.update(am.huddled_state(), 0.0)
+    _invalid(lambda: t.set_obstacle_capsules(), word="before the first update")
+    assert t.obstacle_capsules is None
+
+    # a capsule handle
+    c = mk()
+    c.set_obstacle_avoidance()
+    caps = am.ObstacleCapsules((0.0, 0.2, 0.1, 0.1, 0.1, 0.1, 0.1, 0.3))
+    c.set_obstacle_capsules(caps)
+    assert c.obstacle_capsules == caps
+    c.set_obstacles([post, ball, am.SphereObstacle((2, 2, 1), 0.1, mask=am.MASK_SEGMENTS), am.HalfSpaceObstacle((0, 0, -1), (0, 0, 1), mask=CS.ARM)], 0.5)
+    got, when = c.obstacles()
+    assert [type(o) for o in got] == [am.CapsuleObstacle, am.SphereObstacle, am.SphereObstacle, am.HalfSpaceObstacle] and when == 0.5
+    assert got[0].mask == am.MASK_ALL | am.MASK_SEGMENTS and np.array_equal(got[0].axis, [0, 0, 2])
+    for bit in list(range(9, 16)) + list(range(24, 32)):
+        _invalid(lambda: c.set_obstacles([am.CapsuleObstacle((2, 2, 0), (0, 0, 2), 0.05, mask=1 << bit)], 0.0), word="mask")
+        _invalid(lambda: c.set_obstacles([am.SphereObstacle((2, 2, 1), 0.1, mask=(1 << bit) | 1)], 0.0), word="mask")
+    for axis in ((0, np.nan, 1), (np.inf, 0, 0), (0, 0, -np.inf)):
+        _invalid(lambda: c.set_obstacles([am.CapsuleObstacle((2, 2, 0), axis, 0.05)], 0.0), word="finite")
+    _invalid(lambda: c.set_obstacles([am.CapsuleObstacle((2, 2, 0), (0, 0, 2), -0.05)], 0.0), word="radius")
+    _invalid(lambda: c.set_obstacles([am.HalfSpaceObstacle((0, 0, 0), (0, 0, 2.0), mask=CS.ARM)], 0.0), word="unit")   # still a unit normal
+    unknown = am.SphereObstacle((2, 2, 1), 0.1)
+    unknown.kind = 3
+    _invalid(lambda: c.set_obstacles([unknown], 0.0), word="kind")
+    assert len(c.obstacles()[0]) == 4   # the refused calls left the set in place
+    c.set_obstacles([am.CapsuleObstacle((2, 2, 0), (0, 0, 0), 0.0), am.CapsuleObstacle((2, 2, 0), (0, 0, 1e-300), 0.05, mask=0)], 0.0)   # any finite axis
+    c.update(am.huddled_state(), 0.0)
+    c.set_obstacles([post], 0.0)
+    c.update(am.huddled_state(), 0.01)
+    assert c.update_info()["wait_timeouts"] == 0 and c.get_optimal_obstacle_cost() > 0.0
+    _invalid(lambda: c.set_obstacle_capsules(), word="before the first update")
+    assert c.obstacle_capsules == caps
+
+
+# ---- 6. the C++ surface --------------------------------------------------------------------------
+
+def test_cpp_capsule_surface_on_the_device(monkeypatch):
+    _set_env(monkeypatch)
+    cpp = os.path.join(REPO, "tests", "cpp")
+    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "capsules.mk"])
+    out = subprocess.check_output([os.path.join(cpp, "build", "capsules"), "gpu"], timeout=300).decode()
+    lines = [json.loads(l) for l in out.strip().split("\n")]
+    assert lines[0] == {"cpu": "ok"}
+    assert lines[1] == {"before_avoidance": False, "reports": False}
+    assert lines[2] == {"enabled": True, "radius7": 0.03, "capsule_refused_without": True}
+    assert lines[3] == {"count": 2, "kind0": abi.MPPI_OBSTACLE_CAPSULE, "mask1": CS.ARM, "axis_z": 2.0}
+    assert lines[4]["with_set"] > 0.0 and lines[4]["cleared"] == 0.0 and lines[4]["late_enable"] is False
+    # the object's cost: the same program's inputs through the Python object
+    caps = am.ObstacleCapsules((0.1,) + (0.06,) * 6 + (0.03,))
+    obstacles = [am.CapsuleObstacle((2.0, 2.0, 0.0), (0.0, 0.0, 2.0), 0.05, velocity=(-0.5, 0, 0)),
+                 am.SphereObstacle((0.7106, 0.7176, 1.1857), 0.03, mask=CS.ARM)]
+    d = am.PinocchioDynamicsObject.create(am.huddled_state(), link_positions=True)
+    d.set_state(am.huddled_state(), 0.0)
+    d.step(np.array([(5.0 - i) if 3 <= i < 10 else 0.1 for i in range(12)]), 0.01)
+    assert lines[5]["same"] and lines[5]["object_cost"] == d.capsule_cost(None, caps, obstacles, 0.3)
