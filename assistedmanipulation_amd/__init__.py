@@ -21,6 +21,7 @@ from .trajectory import (AssistedManipulation, Cost, Dynamics, EngineError, Trac
 from .obstacles import (CapsuleObstacle, HalfSpaceObstacle, ObstacleAvoidance, ObstacleCapsules, SphereObstacle,  # noqa: E402
                         MASK_ALL, MASK_SEGMENTS, mask_segment, obstacle_clearance, obstacle_from_c, obstacles_to_c,
                         segment_distance)
+from .distance_field import DistanceField, field_clearance  # noqa: E402
 from .safety import TrajectorySafetyFilter  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
 from .dynamics import DynamicsForecast, EndEffectorState, PinocchioDynamicsObject, evaluate_cost  # noqa: E402
@@ -33,5 +34,5 @@ __all__ = [
     "EngineError", "FrankaRidgebackDynamics", "PointMassDynamics", "QuadraticCost", "Trajectory",
     "comm_unique_id", "shard_range", "Predicted", "ObstacleAvoidance", "SphereObstacle", "HalfSpaceObstacle",
     "obstacle_clearance", "TrajectorySafetyFilter", "CapsuleObstacle", "ObstacleCapsules", "MASK_ALL", "MASK_SEGMENTS",
-    "mask_segment", "obstacle_from_c", "obstacles_to_c", "segment_distance",
+    "mask_segment", "obstacle_from_c", "obstacles_to_c", "segment_distance", "DistanceField", "field_clearance",
 ]

@@ -117,6 +117,13 @@ PROTOTYPES = {
     "mppi_get_obstacle_capsules": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_capsule_config)]),
     "mppi_dynamics_capsule_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_capsule_config),
                                              C.POINTER(abi.mppi_obstacle), C.c_int32, C.c_double, _dp]),
+    "mppi_set_distance_field_avoidance": (C.c_int, [_h]),
+    "mppi_get_distance_field_avoidance": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_set_distance_field": (C.c_int, [_h, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float)]),
+    "mppi_get_distance_field": (C.c_int, [_h, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_int)]),
+    "mppi_optimal_field_cost": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_distance_field_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_capsule_config),
+                                                    C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float), _dp]),
 }
 
 _lib = None

@@ -179,6 +179,18 @@ class mppi_capsule_config(C.Structure):
     _fields_ = [("segment_radii", _d * MPPI_OBSTACLE_SEGMENTS)]
 
 
+# mppi_set_distance_field
+MPPI_DISTANCE_FIELD_MIN_DIM = 2
+MPPI_DISTANCE_FIELD_MAX_DIM = 512
+MPPI_DISTANCE_FIELD_MAX_VALUES = 1 << 24
+MPPI_DISTANCE_FIELD_MAX_SAMPLES = 8
+
+
+class mppi_distance_field(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("segment_samples", C.c_int32), ("mask", C.c_uint32), ("pad", C.c_int32),
+                ("origin", _d * 3), ("voxel", C.c_double)]
+
+
 class mppi_safety_filter_desc(C.Structure):
     """TrajectorySafetyFilter::Configuration (frankaridgeback/safety.hpp:15-40) -> include/mppi_amd.h."""
     _fields_ = [

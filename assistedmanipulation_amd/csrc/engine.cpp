@@ -125,6 +125,66 @@ bool check_capsule_config(const mppi_capsule_config &c, std::string &why)
     return true;
 }
 
+// mppi_set_distance_field's / mppi_dynamics_distance_field_cost's descriptor and values
+bool check_distance_field(const mppi_distance_field &f, const float *values, std::string &why)
+{
+    int64_t n = 1;
+    for (int a = 0; a < 3; a++) {
+        if (f.dims[a] < MPPI_DISTANCE_FIELD_MIN_DIM || f.dims[a] > MPPI_DISTANCE_FIELD_MAX_DIM) {
+            why = "distance field: dims[" + std::to_string(a) + "] must be in [2, 512]";
+            return false;
+        }
+        n *= f.dims[a];
+    }
+    if (n > MPPI_DISTANCE_FIELD_MAX_VALUES) {
+        why = "distance field: the product of dims must be <= 2^24";
+        return false;
+    }
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(f.origin[a])) {
+            why = "distance field: origin must be finite";
+            return false;
+        }
+    if (!std::isfinite(f.voxel) || f.voxel <= 0.0) {
+        why = "distance field: voxel must be finite and > 0";
+        return false;
+    }
+    if (f.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS)) {
+        why = "distance field: mask has bits outside the points (0..8) and the segments (16..23)";
+        return false;
+    }
+    if (f.segment_samples < 0 || f.segment_samples > MPPI_DISTANCE_FIELD_MAX_SAMPLES) {
+        why = "distance field: segment_samples must be in [0, 8]";
+        return false;
+    }
+    if (!values) {
+        why = "distance field: values is NULL";
+        return false;
+    }
+    for (int64_t i = 0; i < n; i++)
+        if (!std::isfinite(values[i])) {
+            why = "distance field: values[" + std::to_string(i) + "] is not finite";
+            return false;
+        }
+    return true;
+}
+
+// The table's second tail of a checked descriptor and its device grid: inv_voxel and the segments'
+// fractions phi_j = j / (m + 1) are made here, in fp64 (the device never divides)
+void fill_field(DevField &d, const mppi_distance_field &f, const float *grid)
+{
+    d.grid = grid;
+    for (int a = 0; a < 3; a++) {
+        d.dims[a] = f.dims[a];
+        d.origin[a] = f.origin[a];
+    }
+    d.mask = f.mask;
+    d.inv_voxel = 1.0 / f.voxel;
+    d.samples = f.segment_samples;
+    for (int j = 0; j < OB_FIELD_SAMPLES; j++)
+        d.phi[j] = j < f.segment_samples ? (double)(j + 1) / (double)(f.segment_samples + 1) : 0.0;
+}
+
 // mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set (capsules: a capsule handle's, or
 // mppi_dynamics_capsule_cost's - the capsule kind and the segment bits of a mask are legal)
 bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why, bool capsules = false)
@@ -312,6 +372,21 @@ struct mppi_handle {
     // (FR_LINKS_CAPSULES), fixed once enabled like avoidance itself
     bool obstacle_capsules = false;
     mppi_capsule_config cap_config{};
+    // mppi_set_distance_field_avoidance: the field kernels (FR_LINKS_FIELD), fixed once enabled.
+    // mppi_set_distance_field: the descriptor and two device grids.  A set writes the grid that the
+    // last update's table does not reference (field_last; -1: none), behind the stream's earlier
+    // launches, through a pinned staging copy (ev_field: that copy has left the staging buffer);
+    // field_cur is the grid that holds the current field.  An update's table names field_cur, so its
+    // filter() row, standalone or folded into the next launch, reads its own update's grid whatever
+    // was set since.
+    bool field_avoidance = false, field_present = false;
+    mppi_distance_field field{};
+    float *d_field[2] = {nullptr, nullptr};
+    size_t field_cap[2] = {0, 0};
+    int field_cur = 0, field_last = -1;
+    float *h_field_stage = nullptr;
+    size_t field_stage_cap = 0;
+    hipEvent_t ev_field = nullptr;
     // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
     // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
     // (phase3_launch).  safety_ran: the last phase 3 ran it (d_out_stage holds that update's
@@ -1158,6 +1233,44 @@ mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_con
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
+                                              const mppi_capsule_config *capsules, const mppi_distance_field *field,
+                                              const float *values, double *cost)
+{
+    if (!d || !cost) return MPPI_ERR_INVALID;
+    if (d->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return dfail(d, MPPI_ERR_INVALID, "distance field cost needs the kinematic link-position model (mppi_dynamics_set_link_positions)");
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    mppi_capsule_config cc;
+    if (capsules) cc = *capsules;
+    else mppi_default_capsule_config(&cc);
+    std::string why;
+    if (!check_obstacle_config(c, why) || !check_capsule_config(cc, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (!field) {   // no field: no term
+        *cost = 0.0;
+        return MPPI_OK;
+    }
+    if (!check_distance_field(*field, values, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    DHIP_TRY(hipSetDevice(d->device));
+    const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
+    float *grid = nullptr;
+    DHIP_TRY(hipMalloc((void **)&grid, n * sizeof(float)));
+    ObstacleTable t{};
+    fill_obstacle_table(t, c, nullptr, 0, 0.0, 0.0, &cc);
+    fill_field(t.field, *field, grid);
+    hipError_t e = hipMemcpyAsync(grid, values, n * sizeof(float), hipMemcpyHostToDevice, d->stream);
+    if (e == hipSuccess) e = launch_fr_object_field(d->d_obj, t, d->d_buf, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    (void)hipFree(grid);
+    DHIP_TRY(e);
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
                                         double *out12)
 {
@@ -1532,6 +1645,8 @@ void mppi_destroy(mppi_handle *h)
     for (void *p : h->allocations) (void)hipFree(p);
     if (h->h_out) (void)hipHostFree(h->h_out);
     if (h->h_opt) (void)hipHostFree(h->h_opt);
+    if (h->h_field_stage) (void)hipHostFree(h->h_field_stage);
+    if (h->ev_field) (void)hipEventDestroy(h->ev_field);
     if (h->ev_pub) (void)hipEventDestroy(h->ev_pub);
     if (h->ev_opt_done) (void)hipEventDestroy(h->ev_opt_done);
     if (h->ev_opt_end) (void)hipEventDestroy(h->ev_opt_end);
@@ -1908,6 +2023,7 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
 // FrRolloutArgs::link_positions of the handle's launches
 static int launch_link_mode(const mppi_handle *h)
 {
+    if (h->obstacle_avoidance && h->field_avoidance) return FR_LINKS_FIELD;
     if (h->obstacle_avoidance) return h->obstacle_capsules ? FR_LINKS_CAPSULES : FR_LINKS_OBSTACLES;
     return h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? FR_LINKS_KINEMATIC : FR_LINKS_ZERO;
 }
@@ -2010,6 +2126,10 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
     h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
     ObstacleTable t{};
     fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time, h->obstacle_capsules ? &h->cap_config : nullptr);
+    if (h->field_avoidance) {   // the current field's grid: the next set leaves it alone
+        if (h->field_present) fill_field(t.field, h->field, h->d_field[h->field_cur]);
+        h->field_last = h->field_present ? h->field_cur : -1;
+    }
     HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
     return MPPI_OK;
 }
@@ -2934,6 +3054,78 @@ mppi_status mppi_get_obstacle_capsules(mppi_handle *h, int *enabled, mppi_capsul
     return MPPI_OK;
 }
 
+mppi_status mppi_set_distance_field_avoidance(mppi_handle *h)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->obstacle_capsules)
+        return fail(h, MPPI_ERR_INVALID, "distance field avoidance: obstacle capsules are not enabled (mppi_set_obstacle_capsules)");
+    // the field kernels are part of the launch plan and of a captured graph, like the capsule kernels
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "distance field avoidance is enabled before the first update");
+    h->field_avoidance = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_distance_field_avoidance(mppi_handle *h, int *enabled)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->field_avoidance ? 1 : 0;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *field, const float *values)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->field_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "distance field: field avoidance is not enabled (mppi_set_distance_field_avoidance)");
+    if (!field) {   // no field from the next update on; the grids stay for the tables that name them
+        h->field_present = false;
+        return MPPI_OK;
+    }
+    std::string why;
+    if (!check_distance_field(*field, values, why)) return fail(h, MPPI_ERR_INVALID, why);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
+    // the grid the last update's table does not reference: that update's filter() row may not have run
+    // yet.  Two sets between the same two updates both land here.
+    const int b = h->field_last == 0 ? 1 : 0;
+    if (!h->ev_field) HIP_TRY(hipEventCreateWithFlags(&h->ev_field, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(h->ev_field));   // the previous set's copy has read the staging buffer
+    if (n > h->field_stage_cap) {
+        if (h->h_field_stage) (void)hipHostFree(h->h_field_stage);
+        h->h_field_stage = nullptr;
+        h->field_stage_cap = 0;
+        HIP_TRY(hipHostMalloc((void **)&h->h_field_stage, n * sizeof(float), hipHostMallocDefault));
+        h->field_stage_cap = n;
+    }
+    if (n > h->field_cap[b]) {   // (every launch that read this grid is behind a later update's publish)
+        dfree(h, h->d_field[b]);
+        h->field_cap[b] = 0;
+        void *q = nullptr;   // (not dalloc: its zero-fill runs on the null stream, unordered with the copy below, which overwrites every value)
+        HIP_TRY(hipMalloc(&q, n * sizeof(float)));
+        h->allocations.push_back(q);
+        h->d_field[b] = (float *)q;
+        h->field_cap[b] = n;
+    }
+    std::memcpy(h->h_field_stage, values, n * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(h->d_field[b], h->h_field_stage, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_field, h->stream));
+    h->field = *field;
+    h->field.pad = 0;
+    h->field_present = true;
+    h->field_cur = b;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, int *present)
+{
+    if (!h || !present) return MPPI_ERR_INVALID;
+    if (!h->field_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "distance field: field avoidance is not enabled (mppi_set_distance_field_avoidance)");
+    *present = h->field_present ? 1 : 0;
+    if (h->field_present && out) *out = h->field;
+    return MPPI_OK;
+}
+
 mppi_status mppi_set_graph(mppi_handle *h, int enable)
 {
     if (!h || enable < 0 || enable > 1) return MPPI_ERR_INVALID;
@@ -3225,6 +3417,27 @@ mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
     // (the row's own update's table: behind opt_steps)
     HIP_TRY(launch_fr_obstacle_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
                                      h->stream_opt, h->obstacle_capsules));
+    if (h->field_avoidance)   // a field handle: the capsule term plus the field term
+        HIP_TRY(launch_fr_field_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 1,
+                                      h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, (h->field_avoidance ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    HIP_TRY(hipStreamSynchronize(h->stream_opt));
+    *cost = h->field_avoidance ? h->h_opt[1] + h->h_opt[2] : h->h_opt[1];
+    return MPPI_OK;
+}
+
+mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost)
+{
+    if (!h || !cost) return MPPI_ERR_INVALID;
+    if (!h->field_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "field cost: distance field avoidance is not enabled");
+    HIP_TRY(hipSetDevice(h->device));
+    *cost = 0.0;
+    if (!h->published_once) return MPPI_OK;   // no filter() row yet
+    mppi_status st = wait_optimal(h);
+    if (st != MPPI_OK) return st;
+    // (the row's own update's table, and through it that update's grid)
+    HIP_TRY(launch_fr_field_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
+                                  h->stream_opt));
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->h_opt[1];

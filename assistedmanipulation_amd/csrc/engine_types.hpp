@@ -101,6 +101,21 @@ constexpr int OB_SPHERE = 0, OB_HALF_SPACE = 1, OB_CAPSULE = 2;
 constexpr int OB_SEGMENTS = 8, OB_SEGMENT_BIT0 = 16;
 // what the objective's obstacle term tests: nothing, the nine points, or points and segments
 constexpr int OB_TERM_NONE = 0, OB_TERM_POINTS = 1, OB_TERM_CAPSULES = 2;
+// ... or points and segments and, behind them, a signed-distance grid (mppi_set_distance_field_avoidance)
+constexpr int OB_TERM_FIELD = 3;
+// The distance field of one update: the grid (fp32, (nx, ny, nz) C order, z fastest; null: no field),
+// its frame and what is sampled - the points of mask bits 0..8, and on the segments of bits 16..23
+// `samples` interior points at the fractions phi[j] = (j + 1) / (samples + 1), made on the host.
+constexpr int OB_FIELD_SAMPLES = 8;
+struct DevField {
+    const float *grid;
+    int dims[3];
+    unsigned mask;
+    double origin[3];
+    double inv_voxel;
+    int samples, pad;
+    double phi[OB_FIELD_SAMPLES];
+};
 struct DevObstacle {
     double position[3], velocity[3], normal[3], radius;
     int kind;
@@ -113,6 +128,7 @@ struct ObstacleTable {
     int count, pad;
     DevObstacle ob[OB_MAX];
     double seg_radii[OB_SEGMENTS];   // capsule handles only (zeros otherwise)
+    DevField field;                  // field handles only (zeros otherwise): behind everything the other kernels read
 };
 // the table's room behind the 2 H step-constant slots, in StepConst units
 constexpr int OB_TABLE_STEPS = (int)((sizeof(ObstacleTable) + sizeof(StepConst) - 1) / sizeof(StepConst));

@@ -58,12 +58,13 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
-// This text is compiled as eight translation units: by itself (the default mode's kernels
+// This text is compiled as ten translation units: by itself (the default mode's kernels
 // and everything the host calls), and included by fr_coop_lp.hip (FR_COOP_LP_UNIT: the kinematic
 // link-position objective), fr_coop_wr.hip (FR_COOP_WR_UNIT: the simulated end-effector wrench in
 // the step), fr_coop_wr_lp.hip (both), and fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip (FR_COOP_OB_UNIT
 // on top of LP: the obstacle term in the objective), and fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip
-// (FR_COOP_CAP_UNIT on top of OB: the obstacle term with segments and capsule obstacles).  A variant
+// (FR_COOP_CAP_UNIT on top of OB: the obstacle term with segments and capsule obstacles), and
+// fr_coop_lp_df.hip and fr_coop_wr_lp_df.hip (FR_COOP_DF_UNIT on top of CAP: the distance field).  A variant
 // unit holds its kernels and their launchers only.
 #if defined(FR_COOP_LP_UNIT) || defined(FR_COOP_WR_UNIT)
 #define FR_COOP_VARIANT_UNIT 1
@@ -74,7 +75,12 @@ using mppi_dev::smin;
 #if defined(FR_COOP_CAP_UNIT) && !defined(FR_COOP_OB_UNIT)
 #error "the capsule units are obstacle units"
 #endif
-#if defined(FR_COOP_CAP_UNIT)
+#if defined(FR_COOP_DF_UNIT) && !defined(FR_COOP_CAP_UNIT)
+#error "the distance-field units are capsule units"
+#endif
+#if defined(FR_COOP_DF_UNIT)
+#define FR_UNIT_OB OB_TERM_FIELD
+#elif defined(FR_COOP_CAP_UNIT)
 #define FR_UNIT_OB OB_TERM_CAPSULES
 #elif defined(FR_COOP_OB_UNIT)
 #define FR_UNIT_OB OB_TERM_POINTS
@@ -2322,8 +2328,19 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // again kernels and units of their own (fr_coop_wr.hip; with LP, fr_coop_wr_lp.hip).
 // OB: the obstacle term in the LP objective (FrRolloutArgs::link_positions == 2), units
 // fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip; with segments and capsule obstacles (== 3), units
-// fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip.
-#if defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
+// fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip; with the distance field (== 4), units fr_coop_lp_df.hip
+// and fr_coop_wr_lp_df.hip.
+#if defined(FR_COOP_DF_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_COOP_K fr_coop_wr_lp_df_kernel
+#define FR_COOP_XK fr_coop_x_wr_lp_df_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR true
+#elif defined(FR_COOP_DF_UNIT)
+#define FR_COOP_K fr_coop_lp_df_kernel
+#define FR_COOP_XK fr_coop_x_lp_df_kernel
+#define FR_UNIT_LP true
+#define FR_UNIT_WR false
+#elif defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
 #define FR_COOP_K fr_coop_wr_lp_cap_kernel
 #define FR_COOP_XK fr_coop_x_wr_lp_cap_kernel
 #define FR_UNIT_LP true
@@ -2414,6 +2431,8 @@ FR_UNIT_DECL(lp_ob)
 FR_UNIT_DECL(wr_lp_ob)
 FR_UNIT_DECL(lp_cap)
 FR_UNIT_DECL(wr_lp_cap)
+FR_UNIT_DECL(lp_df)
+FR_UNIT_DECL(wr_lp_df)
 #undef FR_UNIT_DECL
 
 template <int CK, bool EN, int WPB, bool KC>
@@ -2434,6 +2453,8 @@ template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_FIELD)
+        return a.simulated_wrench ? launch_fr_coop_wr_lp_df_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_df_one(a, nb, s, WPB, KC);
     if (a.link_positions == FR_LINKS_CAPSULES)
         return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_cap_one(a, nb, s, WPB, KC);
     if (a.link_positions == FR_LINKS_OBSTACLES)
@@ -2449,6 +2470,7 @@ static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
 #ifndef FR_COOP_VARIANT_UNIT
+    if (a.link_positions == FR_LINKS_FIELD) return a.simulated_wrench ? launch_fr_coop_wr_lp_df_x(a, nb, s) : launch_fr_coop_lp_df_x(a, nb, s);
     if (a.link_positions == FR_LINKS_CAPSULES) return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_x(a, nb, s) : launch_fr_coop_lp_cap_x(a, nb, s);
     if (a.link_positions == FR_LINKS_OBSTACLES) return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_x(a, nb, s) : launch_fr_coop_lp_ob_x(a, nb, s);
     if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_x(a, nb, s) : launch_fr_coop_wr_x(a, nb, s);
@@ -2460,7 +2482,11 @@ static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 }
 
 #ifdef FR_COOP_VARIANT_UNIT
-#if defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
+#if defined(FR_COOP_DF_UNIT) && defined(FR_COOP_WR_UNIT)
+#define FR_UNIT_FN(pre, post) pre##wr_lp_df##post
+#elif defined(FR_COOP_DF_UNIT)
+#define FR_UNIT_FN(pre, post) pre##lp_df##post
+#elif defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
 #define FR_UNIT_FN(pre, post) pre##wr_lp_cap##post
 #elif defined(FR_COOP_CAP_UNIT)
 #define FR_UNIT_FN(pre, post) pre##lp_cap##post
@@ -2521,7 +2547,8 @@ bool fr_coop_is_update_kernel(const void *f)
            f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
            f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f) ||
            fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f) || fr_coop_lp_ob_is_update_kernel(f) ||
-           fr_coop_wr_lp_ob_is_update_kernel(f) || fr_coop_lp_cap_is_update_kernel(f) || fr_coop_wr_lp_cap_is_update_kernel(f);
+           fr_coop_wr_lp_ob_is_update_kernel(f) || fr_coop_lp_cap_is_update_kernel(f) || fr_coop_wr_lp_cap_is_update_kernel(f) ||
+           fr_coop_lp_df_is_update_kernel(f) || fr_coop_wr_lp_df_is_update_kernel(f);
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at

@@ -339,6 +339,152 @@ __device__ __forceinline__ double capsule_term(TP T, const double (*lp)[3], cons
     return term;
 }
 
+// ---- the distance field (mppi_set_distance_field_avoidance, mppi_set_distance_field) -------------
+// The sensed environment as a signed-distance grid (include/mppi_amd.h has the definition): the
+// step's term is the sum of Left(limit)(D(p) - radius) over the masked points in order, then over
+// the masked segments in order, each at its `samples` interior points a + phi_j (b - a).  D is the
+// trilinear interpolant of the cell that holds p, z then y then x, every operation rounded by itself.
+//
+// field_cell: the cell and the fractions of one world point.  The cell index is clamped twice, as a
+// double before the conversion (fmax and fmin take a NaN to the bound, so the conversion is always in
+// range) and as an integer after it, on every lane whatever it holds: the address below never comes
+// from an unclamped index, and with dims >= 2 (the host's check) all eight corners lie in the grid.
+// st: 0 inside, 1 outside (contributes 0), 2 a NaN coordinate (NaN).
+typedef const __attribute__((address_space(1))) float *FieldGrid;
+struct FieldCell {
+    int idx, st;
+    double f[3];
+};
+template <typename TP>
+__device__ __forceinline__ FieldCell field_cell(TP T, const double *p)
+{
+    // plain operators under contract(off): __dmul_rn and __dadd_rn are inline functions of plain operators
+    // that carry the translation unit's contraction, and once inlined their product and sum fuse into an FMA
+#pragma clang fp contract(off)
+    FieldCell c;
+    int i[3];
+    bool inside = true, nan = false;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const int n = T->field.dims[a];
+        const double g = (p[a] - T->field.origin[a]) * T->field.inv_voxel;
+        inside = inside && g >= 0.0 && g <= (double)(n - 1);
+        nan = nan || g != g;
+        int ia = (int)fmin(fmax(g, 0.0), (double)(n - 2));
+        asm("" : "+v"(ia));   // (the integer clamp stays: the compiler may not reason it away from the double's range)
+        ia = ia > n - 2 ? n - 2 : ia;
+        ia = ia < 0 ? 0 : ia;
+        i[a] = ia;
+        c.f[a] = g - (double)ia;
+    }
+    c.idx = (i[0] * T->field.dims[1] + i[1]) * T->field.dims[2] + i[2];
+    c.st = nan ? 2 : (inside ? 0 : 1);
+    return c;
+}
+__device__ __forceinline__ double field_lerp(double a, double b, double f)
+{
+#pragma clang fp contract(off)
+    return a + f * (b - a);
+}
+
+// The sampled unit u (wave-uniform): 0..8 the points (the segment (p, p)), 9..16 the segments, each
+// case by name like segment_ends, so that the link coordinates stay in registers
+__device__ __forceinline__ void field_ends(const double (*lp)[3], const double *ee, int u, double *a, double *b)
+{
+#define FLD_CASE(n, P, Q) case n: for (int i = 0; i < 3; i++) { a[i] = (P)[i]; b[i] = (Q)[i]; } break;
+    switch (u) {
+        FLD_CASE(0, lp[0], lp[0]) FLD_CASE(1, lp[1], lp[1]) FLD_CASE(2, lp[2], lp[2]) FLD_CASE(3, lp[3], lp[3])
+        FLD_CASE(4, lp[4], lp[4]) FLD_CASE(5, lp[5], lp[5]) FLD_CASE(6, lp[6], lp[6]) FLD_CASE(7, lp[7], lp[7])
+        FLD_CASE(8, ee, ee)
+        FLD_CASE(9, lp[0], lp[1]) FLD_CASE(10, lp[1], lp[2]) FLD_CASE(11, lp[2], lp[3]) FLD_CASE(12, lp[3], lp[4])
+        FLD_CASE(13, lp[4], lp[5]) FLD_CASE(14, lp[5], lp[6]) FLD_CASE(15, lp[6], lp[7])
+        default: for (int i = 0; i < 3; i++) { a[i] = lp[7][i]; b[i] = ee[i]; } break;
+    }
+#undef FLD_CASE
+}
+
+// The step's field term.  One rolled loop over the samples around one copy of the sample, in two
+// halves a sample apart: a trip finds the next sample's cell and issues its eight corner loads (the
+// only per-lane memory reads; everything else is the table's, scalar loads), then interpolates the
+// sample before it and runs its barrier while those loads are in flight.  The loop's control - the
+// masks, the unit and the sample within it - is the wave's; a point is sampled as it is, a segment at
+// a + phi (b - a).  No field (a null grid): nothing is read.
+template <typename TP>
+__device__ __forceinline__ double field_term(TP T, const double (*lp)[3], const double *ee)
+{
+#pragma clang fp contract(off)
+    if (T->field.grid == nullptr) return 0.0;
+    // (global memory, known as such: global_load, not flat_load; the base is the wave's, from the table)
+    const FieldGrid grid = (FieldGrid) reinterpret_cast<uint64_t>(T->field.grid);
+    const int nz = T->field.dims[2], nyz = T->field.dims[1] * nz;
+    const unsigned mask = T->field.mask;
+    int m = T->field.samples;
+    m = m < 0 ? 0 : (m > OB_FIELD_SAMPLES ? OB_FIELD_SAMPLES : m);   // (never past phi, whatever the table holds)
+    // the units left: bits 0..8 the points, bits 9..16 the segments (none with no samples)
+    unsigned rem = (mask & 0x1FFu) | (m > 0 ? ((mask >> OB_SEGMENT_BIT0) & 0xFFu) << OB_POINTS : 0u);
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    double term = 0.0;
+    int u = 0, j = 0, cnt = 0;
+    bool cur = false;                      // a sample is in flight
+    float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    double f[3] = {0.0, 0.0, 0.0}, rad = 0.0;
+    int st = 1;
+#pragma unroll 1
+    for (;;) {
+        bool have = true;
+        if (j + 1 < cnt) j++;
+        else if (rem) {
+            u = __builtin_ctz(rem);
+            rem &= rem - 1u;
+            j = 0;
+            cnt = u >= OB_POINTS ? m : 1;
+        } else have = false;
+        float nc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        FieldCell cell{0, 1, {0.0, 0.0, 0.0}};
+        double nrad = 0.0;
+        if (have) {
+            double a[3], b[3], p[3];
+            field_ends(lp, ee, u, a, b);
+            const bool seg = u >= OB_POINTS;
+            const double phi = seg ? T->field.phi[j] : 0.0;
+            nrad = seg ? T->seg_radii[u - OB_POINTS] : T->radii[seg ? 0 : u];
+#pragma unroll
+            for (int i = 0; i < 3; i++) p[i] = seg ? a[i] + phi * (b[i] - a[i]) : a[i];   // (a point is itself, also an infinite one: outside, 0)
+            cell = field_cell(T, p);
+            // eight dword loads: the z pair's upper address goes through an empty asm, so that the pair is
+            // not merged into one 8-byte load at 4-byte alignment
+            const FieldGrid g = grid + cell.idx;
+            FieldGrid g1 = g + 1;
+            asm("" : "+v"(g1));
+            nc[0] = g[0];
+            nc[1] = g1[0];
+            nc[2] = g[nz];
+            nc[3] = g1[nz];
+            nc[4] = g[nyz];
+            nc[5] = g1[nyz];
+            nc[6] = g[nyz + nz];
+            nc[7] = g1[nyz + nz];
+        }
+        if (cur) {
+            const double z00 = field_lerp((double)c[0], (double)c[1], f[2]), z01 = field_lerp((double)c[2], (double)c[3], f[2]);
+            const double z10 = field_lerp((double)c[4], (double)c[5], f[2]), z11 = field_lerp((double)c[6], (double)c[7], f[2]);
+            const double y0 = field_lerp(z00, z01, f[1]), y1 = field_lerp(z10, z11, f[1]);
+            const double D = field_lerp(y0, y1, f[0]);
+            const double bv = left_barrier(bound, scale, mx, D - rad);
+            term += st == 0 ? bv : (st == 1 ? 0.0 : __builtin_nan(""));
+        }
+        if (!have) break;
+#pragma unroll
+        for (int i = 0; i < 8; i++) c[i] = nc[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) f[i] = cell.f[i];
+        rad = nrad;
+        st = cell.st;
+        cur = true;
+    }
+    return term;
+}
+
 // An update's obstacle table as the rollouts' objective reads it: nothing writes it during a launch
 // (obstacle_table_kernel ran before), so it is addressed in the constant address space, and its
 // address is made the wave's by v_readfirstlane - it is the same on every lane, but where it hangs
@@ -362,8 +508,10 @@ struct ObstacleRef {
     bool frow;
     int k;
 };
-// CAP: the capsule term (capsule_term) instead of obstacle_term
-template <bool CAP = false>
+// TERM: OB_TERM_POINTS obstacle_term, OB_TERM_CAPSULES capsule_term, OB_TERM_FIELD capsule_term and then
+// field_term, both from the same table - the folded filter() row's second pass so reads its own
+// update's grid
+template <int TERM = OB_TERM_POINTS>
 __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt)
 {
     double term = 0.0;
@@ -372,7 +520,8 @@ __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const dou
     for (int pass = 0; pass < np; pass++) {
         const ObstacleTableK T = pass ? ob.ftab : ob.tab;
         double t;
-        if constexpr (CAP) t = capsule_term(T, lp, ee, dt, ob.k);
+        if constexpr (TERM == OB_TERM_FIELD) t = capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee);
+        else if constexpr (TERM == OB_TERM_CAPSULES) t = capsule_term(T, lp, ee, dt, ob.k);
         else t = obstacle_term(T, lp, ee, dt, ob.k);
         term = (pass == 0 || ob.frow) ? t : term;
     }
@@ -463,7 +612,8 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 // (lm, first: record_self_collision) instead of the zero stub's constant
 // OB (with LP): the obstacle term on the same link positions (ob: obstacle_cost), added after the
 // reference's terms; the link FK then runs whether or not the self-collision switch is on.  OB_TERM_NONE,
-// OB_TERM_POINTS (the nine points) or OB_TERM_CAPSULES (points and segments, capsule obstacles)
+// OB_TERM_POINTS (the nine points), OB_TERM_CAPSULES (points and segments, capsule obstacles) or
+// OB_TERM_FIELD (the capsule term and the distance field's)
 template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
                                                              const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
@@ -574,7 +724,7 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
         link_fk(*lm.model, qj, lp);
         double sct = 0.0;
         if (Cs.en_self) sct = self_collision_term<false>(Cs, lp);
-        const double obt = obstacle_cost<OB == OB_TERM_CAPSULES>(ob, lp, pe, lm.dt);
+        const double obt = obstacle_cost<OB>(ob, lp, pe, lm.dt);
         double cost = 0.0;
         cost += t_joint;
         cost += sct;
@@ -723,7 +873,7 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
                 link_fk(*lm.model, qj, lp);
             }
             if constexpr (OB)
-                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost<OB == OB_TERM_CAPSULES>(ob, lp, r + REC_EE, lm.dt));
+                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost<OB>(ob, lp, r + REC_EE, lm.dt));
             else
                 return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
         } else {

@@ -460,7 +460,20 @@ __global__ __launch_bounds__(64) void fr_object_capsule_kernel(const DevPinocchi
     *out1 = mppi_cost::capsule_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, 0.0, 0);
 }
 
+// mppi_dynamics_distance_field_cost: the field term (field_term) at the same positions
+__global__ __launch_bounds__(64) void fr_object_field_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
+{
+    if (threadIdx.x != 0) return;
+    *out1 = mppi_cost::field_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION);
+}
+
 namespace mppi_eng {
+
+hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_object_field_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
+    return hipGetLastError();
+}
 
 hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s, bool capsules)
 {

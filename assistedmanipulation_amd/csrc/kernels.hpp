@@ -124,7 +124,7 @@ struct FinishArgs {
 constexpr int FR_WRENCH_ROW = 8;
 static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows behind the step constants");
 // FrRolloutArgs / FrCostArgs::link_positions
-constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3;
+constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3, FR_LINKS_FIELD = 4;
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -174,6 +174,8 @@ struct FrRolloutArgs {
     // *_ob_kernel units), its table behind the step constants and wrench rows (steps + 2 H, fsteps + 2 H).
     // FR_LINKS_CAPSULES: the obstacle term with segments and capsule obstacles (mppi_set_obstacle_capsules;
     // the *_cap_kernel units), the same table with its tail of segment radii.
+    // FR_LINKS_FIELD: the capsule term and the distance field's (mppi_set_distance_field_avoidance; the
+    // *_df_kernel units), the grid through the same table's second tail.
     int link_positions;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
@@ -524,6 +526,11 @@ hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, i
 // tau = t.t0 - t.t_ref
 // (capsules: mppi_dynamics_capsule_cost, fr_object_capsule_kernel)
 hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s, bool capsules = false);
+// The field term alone: of one rollout's records like launch_fr_obstacle_total (fr_field_total_kernel), and
+// at the object's cached positions (mppi_dynamics_distance_field_cost, fr_object_field_kernel)
+hipError_t launch_fr_field_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                 double dt, double *out1, hipStream_t s);
+hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
 
 
 }  // namespace mppi_eng

@@ -197,6 +197,19 @@ class PinocchioDynamicsObject:
         self._check(self._L.mppi_dynamics_capsule_cost(self._h, C.byref(c), C.byref(cc), arr, n, float(elapsed), C.byref(v)))
         return v.value
 
+    def distance_field_cost(self, config, capsules, field):
+        """mppi_dynamics_distance_field_cost: the distance field's term (Trajectory.set_distance_field)
+        of `field` (a DistanceField) at the positions the object holds, with `config`'s limit and point
+        radii and `capsules`' segment radii (None: the defaults).  The grid is uploaded on every call."""
+        from .obstacles import ObstacleAvoidance, ObstacleCapsules
+        c = (config or ObstacleAvoidance()).to_c()
+        cc = (capsules or ObstacleCapsules()).to_c()
+        f = field.to_c()
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_dynamics_distance_field_cost(self._h, C.byref(c), C.byref(cc), C.byref(f), field.values_ptr(),
+                                                              C.byref(v)))
+        return v.value
+
     def obstacle_cost(self, config, obstacles, elapsed):
         """mppi_dynamics_obstacle_cost: the obstacle term (Trajectory.set_obstacle_avoidance) of
         `obstacles` moved by `elapsed` seconds, at the link and end-effector positions the object

@@ -225,6 +225,7 @@ class Trajectory:
         self.configuration = configuration
         self.dynamics = dynamics
         self.cost = cost
+        self._field_values = None
         R, H, Cc, X = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self._L.mppi_dims(self._h, C.byref(R), C.byref(H), C.byref(Cc), C.byref(X)))
         self.R, self.H, self.C, self.X = R.value, H.value, Cc.value, X.value
@@ -385,6 +386,46 @@ class Trajectory:
         on, c = C.c_int(0), abi.mppi_capsule_config()
         self._check(self._L.mppi_get_obstacle_capsules(self._h, C.byref(on), C.byref(c)))
         return ObstacleCapsules.from_c(c) if on.value else None
+
+    def set_distance_field_avoidance(self):
+        """mppi_set_distance_field_avoidance: a signed-distance grid of the sensed environment in the
+        obstacle term, behind the capsule term.  After set_obstacle_capsules and before the first
+        update; it cannot be undone."""
+        self._check(self._L.mppi_set_distance_field_avoidance(self._h))
+
+    @property
+    def distance_field_avoidance(self):
+        on = C.c_int(0)
+        self._check(self._L.mppi_get_distance_field_avoidance(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_distance_field(self, field):
+        """mppi_set_distance_field: replace the field (a DistanceField; None: no field).  Between any
+        two updates; every rank of a sharded run sets the same one.  The values are copied."""
+        if field is None:
+            self._check(self._L.mppi_set_distance_field(self._h, None, None))
+        else:
+            f = field.to_c()
+            self._check(self._L.mppi_set_distance_field(self._h, C.byref(f), field.values_ptr()))
+        self._field_values = None if field is None else field.values
+
+    @property
+    def distance_field(self):
+        """The current DistanceField (the descriptor from mppi_get_distance_field, with the values
+        this object was given), or None with no field."""
+        f, on = abi.mppi_distance_field(), C.c_int(0)
+        self._check(self._L.mppi_get_distance_field(self._h, C.byref(f), C.byref(on)))
+        if not on.value:
+            return None
+        from .distance_field import DistanceField
+        return DistanceField(self._field_values, list(f.origin), f.voxel, f.mask, f.segment_samples)
+
+    def get_optimal_field_cost(self):
+        """mppi_optimal_field_cost: the field term of the last update's filter() row summed over its
+        steps, undiscounted (get_optimal_obstacle_cost holds it too, beside the capsule term)."""
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_optimal_field_cost(self._h, C.byref(v)))
+        return v.value
 
     def set_obstacles(self, obstacles, time):
         """mppi_set_obstacles: replace the whole set (SphereObstacle / HalfSpaceObstacle, at most 16;

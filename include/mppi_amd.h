@@ -504,6 +504,68 @@ void mppi_default_capsule_config(mppi_capsule_config *out);
 mppi_status mppi_set_obstacle_capsules(mppi_handle *h, const mppi_capsule_config *config);
 mppi_status mppi_get_obstacle_capsules(mppi_handle *h, int *enabled, mppi_capsule_config *out);
 
+/* The sensed environment as a signed-distance grid (mppi_set_distance_field_avoidance): one more part
+ * of the obstacle term, behind the capsule term of the primitives.  What a depth camera and a mapper
+ * (an ESDF, a voxel map) hand over several times a second, boxes and meshes included.
+ *
+ * Field: a regular grid of dims = (nx, ny, nz) samples, each dimension in [2, 512] and
+ * nx ny nz <= 2^24; origin is the world position of sample (0, 0, 0); voxel > 0 is the edge length on
+ * every axis; values are nx ny nz fp32 signed distances in metres, negative inside matter, in the
+ * layout of a C-contiguous (nx, ny, nz) array (z fastest), all finite.  The field does not move; it
+ * is replaced between updates.  The engine computes inv_voxel = 1.0 / voxel once in fp64; the device
+ * never divides.
+ * Sample D(p) at a world point p, every operation rounded by itself (no fused multiply-add):
+ *   g_a = (p_a - origin_a) * inv_voxel                      a = x, y, z
+ *   p is inside iff 0 <= g_a <= n_a - 1 on all three axes
+ *   i_a = min(floor(g_a), n_a - 2)   (the top face belongs to the last cell),   f_a = g_a - i_a
+ *   c[dx][dy][dz] = (double) values[((i_x + dx) ny + (i_y + dy)) nz + (i_z + dz)]
+ *   with L(a, b, f) = a + f (b - a):  along z, then y, then x
+ *     cz[dx][dy] = L(c[dx][dy][0], c[dx][dy][1], f_z),  cy[dx] = L(cz[dx][0], cz[dx][1], f_y),
+ *     D = L(cy[0], cy[1], f_x)
+ * The interpolant is continuous across cell faces.  A point outside the grid contributes exactly 0
+ * (unknown space is free: the caller pads the grid); a NaN coordinate makes the contribution NaN.
+ * What is sampled: the robot's nine points and eight segments of the capsule handle, with their
+ * lag.  mask has the obstacle masks' bit meanings (bits 0..8 points, bits 16..23 segments), and
+ * segment_samples m in [0, 8].  Point i gives v = D(p_i) - radii[i]; segment s gives, for j = 1..m,
+ * p = p_s + phi_j (p_{s+1} - p_s), phi_j = j / (m + 1) computed on the host in fp64, and
+ * v = D(p) - segment_radii[s] (the end points belong to the point bits; the zero-length segments 1
+ * and 5 sample one point m times; a point is sampled as it is, with no arithmetic on it).  The step's term is the sum of Left(limit)(v) over the masked
+ * points in index order, then the masked segments in index order, each segment's samples in order j,
+ * with the avoidance configuration's limit; it is added to the capsule term, before gamma^k.
+ *
+ * mppi_set_distance_field_avoidance selects the field kernels for the handle's life: after
+ * mppi_set_obstacle_capsules and before the first update (MPPI_ERR_INVALID otherwise, the message
+ * says which).  mppi_set_distance_field replaces the field between any two updates (field NULL:
+ * no field, values ignored); the values are copied before it returns control of them (the caller's
+ * array may be reused once the call returns).  MPPI_ERR_INVALID for a dimension or the product out of
+ * range, a non-finite value, origin or voxel, voxel <= 0, a mask bit outside 0..8 and 16..23, or
+ * segment_samples outside [0, 8]; a refused call leaves the field in place.  Not to be called
+ * concurrently with an update; on sharded handles every rank sets the same field.  The filter() row
+ * of an update reads that update's field, also when the field was replaced before the row ran.
+ * mppi_get_distance_field: the descriptor only; present = 0 with no field (out untouched).
+ * mppi_optimal_field_cost: the field term of the last filter() row summed over its steps,
+ * undiscounted (0 with no field or before the first published update; MPPI_ERR_UNSUPPORTED on a
+ * handle without field avoidance); mppi_optimal_obstacle_cost returns the capsule term plus the
+ * field term on a field handle.  Added like the capsule symbols, without a version change: detect
+ * by symbol. */
+#define MPPI_DISTANCE_FIELD_MIN_DIM 2
+#define MPPI_DISTANCE_FIELD_MAX_DIM 512
+#define MPPI_DISTANCE_FIELD_MAX_VALUES (1 << 24)
+#define MPPI_DISTANCE_FIELD_MAX_SAMPLES 8
+typedef struct mppi_distance_field {
+    int32_t dims[3];
+    int32_t segment_samples;
+    uint32_t mask;
+    int32_t pad;
+    double origin[3];
+    double voxel;
+} mppi_distance_field;
+mppi_status mppi_set_distance_field_avoidance(mppi_handle *h);
+mppi_status mppi_get_distance_field_avoidance(mppi_handle *h, int *enabled);
+mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *field, const float *values);
+mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, int *present);
+mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost);
+
 /* The trajectory safety filter: FrankaRidgeback::TrajectorySafetyFilter::Configuration
  * (frankaridgeback/safety.hpp:15-40) field for field.  The reference declares the class and leaves
  * its methods empty; here the configuration is live, opt-in (no filter unless one is set).  The
@@ -776,6 +838,12 @@ mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_co
  * (NULL: the defaults), capsule obstacles and segment mask bits legal. */
 mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_capsule_config *capsules,
                                        const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost);
+/* The distance field's term (mppi_set_distance_field above) of `field` / `values` at the same positions,
+ * with `config`'s limit and point radii and `capsules`' segment radii (NULL: the defaults).  Stateless:
+ * the grid is uploaded on every call - a diagnostic path. */
+mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
+                                              const mppi_capsule_config *capsules, const mppi_distance_field *field,
+                                              const float *values, double *cost);
 /* add_end_effector_simulated_wrench (6 doubles: force, moment; semantics above): cumulative; the
  * next mppi_dynamics_step applies the sum and zeroes it.  get_end_effector_simulated_wrench: the
  * wrench the last step applied, zeros before any step. */

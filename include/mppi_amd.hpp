@@ -318,6 +318,29 @@ public:
         int on = 0;
         return mppi_get_obstacle_capsules(m_h, &on, out) == MPPI_OK && on != 0;
     }
+    // A signed-distance grid of the sensed environment behind the capsule term
+    // (mppi_set_distance_field_avoidance): after set_obstacle_capsules, before the first update; false
+    // and a message on stderr otherwise.
+    bool set_distance_field_avoidance()
+    {
+        if (mppi_set_distance_field_avoidance(m_h) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // the field (mppi_set_distance_field; nullptr: no field), replaced between any two updates
+    bool set_distance_field(const mppi_distance_field *field, const float *values)
+    {
+        if (mppi_set_distance_field(m_h, field, values) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // the field term of the optimal rollout, summed over its steps (mppi_optimal_field_cost)
+    double get_optimal_field_cost()
+    {
+        double c = 0.0;
+        if (mppi_optimal_field_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
+        return c;
+    }
     // the whole set, given at reference time `time` (mppi_set_obstacles): between any two updates
     bool set_obstacles(const std::vector<mppi_obstacle> &obstacles, double time)
     {
@@ -646,6 +669,14 @@ public:
     {
         double c = 0.0;
         check(mppi_dynamics_capsule_cost(object(), config, capsules, obstacles.data(), (int32_t)obstacles.size(), elapsed, &c));
+        return c;
+    }
+    // the distance field's term at the same positions (mppi_dynamics_distance_field_cost; the grid is uploaded on every call)
+    double distance_field_cost(const mppi_distance_field &field, const float *values, const mppi_obstacle_config *config = nullptr,
+                               const mppi_capsule_config *capsules = nullptr)
+    {
+        double c = 0.0;
+        check(mppi_dynamics_distance_field_cost(object(), config, capsules, &field, values, &c));
         return c;
     }
     std::vector<double> get_joint_position() { return query(0, 12); }
