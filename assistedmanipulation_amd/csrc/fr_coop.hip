@@ -32,8 +32,28 @@
 // Semantics are those of fr_rollout_kernel (PinocchioDynamics::step + AssistedManipulation,
 // one-step kinematic lag, NaN stop); only the association order of sums and products differs.
 // The rollout runs all H - 1 steps: a NaN step cost makes the rollout's sum NaN whatever follows.
+//
+// Units.  This text is compiled ten times, once per cell of a 5 x 2 grid: -DFR_UNIT_LINKS=l,
+// the link mode FR_LINKS_ZERO .. FR_LINKS_FIELD (FrRolloutArgs::link_positions: the reference's stub,
+// the kinematic link-position objective, then the obstacle term on points, on segments and capsules,
+// and with the distance field behind them), and -DFR_UNIT_WR=w, the simulated end-effector wrench in
+// the step off or on (FrRolloutArgs::simulated_wrench).  Both default to 0.  A unit holds its cell's
+// two kernels, named fr_coop_[x_][wr_]<links>kernel with <links> one of "", lp_, lp_ob_, lp_cap_,
+// lp_df_, and their launchers, FrCoopUnit<l, w>'s members; cell (0, 0), the default unit, holds also
+// the table kernel and everything the host calls, which picks a unit from a table over the grid.  The
+// Makefile builds the ten objects from one rule.  The kernels are units apart because in one unit they
+// changed each other's code: apart, a cell's instruction stream does not depend on the other cells.
+#ifndef FR_UNIT_LINKS
+#define FR_UNIT_LINKS 0
+#endif
+#ifndef FR_UNIT_WR
+#define FR_UNIT_WR 0
+#endif
+#define FR_UNIT_DEFAULT (FR_UNIT_LINKS == 0 && FR_UNIT_WR == 0)
 
 #include <hip/hip_runtime.h>
+#include <array>
+#include <utility>
 #include <algorithm>
 #include <math.h>
 #include <stdint.h>
@@ -51,6 +71,13 @@ using namespace mppi_eng;
 using mppi_dev::smax;
 using mppi_dev::smin;
 
+// the unit's cell, and what follows from it: the link-position objective, and its obstacle term
+static_assert(FR_UNIT_LINKS >= FR_LINKS_ZERO && FR_UNIT_LINKS <= FR_LINKS_FIELD && (FR_UNIT_WR == 0 || FR_UNIT_WR == 1), "no such unit");
+static_assert(OB_TERM_NONE == 0 && FR_LINKS_OBSTACLES - 1 == OB_TERM_POINTS && FR_LINKS_CAPSULES - 1 == OB_TERM_CAPSULES &&
+                  FR_LINKS_FIELD - 1 == OB_TERM_FIELD, "a link mode past the kinematic one is its obstacle term + 1");
+constexpr bool UNIT_LP = FR_UNIT_LINKS != FR_LINKS_ZERO, UNIT_WR = FR_UNIT_WR != 0;
+constexpr int UNIT_OB = FR_UNIT_LINKS > FR_LINKS_KINEMATIC ? FR_UNIT_LINKS - 1 : OB_TERM_NONE;
+
 // PHASE_MARKS (analysis builds only, tools/phase_flops.py): a comment at each phase boundary of the
 // step, so that the executed instructions can be attributed to phases - 0 the control and the base
 // velocity, 1 FK (with the next step's sincos), 2 world inertias, 3 kinematics for the cost, 4 the
@@ -58,36 +85,6 @@ using mppi_dev::smin;
 // record stores.  (A volatile asm ends the scheduler's region: the marked build is a little slower.)
 // PMARK_D ties the marker to a value the next phase's inline-asm blocks consume or the previous
 // one's produce: non-volatile asm statements are otherwise free to move across a plain marker.
-// This text is compiled as ten translation units: by itself (the default mode's kernels
-// and everything the host calls), and included by fr_coop_lp.hip (FR_COOP_LP_UNIT: the kinematic
-// link-position objective), fr_coop_wr.hip (FR_COOP_WR_UNIT: the simulated end-effector wrench in
-// the step), fr_coop_wr_lp.hip (both), and fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip (FR_COOP_OB_UNIT
-// on top of LP: the obstacle term in the objective), and fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip
-// (FR_COOP_CAP_UNIT on top of OB: the obstacle term with segments and capsule obstacles), and
-// fr_coop_lp_df.hip and fr_coop_wr_lp_df.hip (FR_COOP_DF_UNIT on top of CAP: the distance field).  A variant
-// unit holds its kernels and their launchers only.
-#if defined(FR_COOP_LP_UNIT) || defined(FR_COOP_WR_UNIT)
-#define FR_COOP_VARIANT_UNIT 1
-#endif
-#if defined(FR_COOP_OB_UNIT) && !defined(FR_COOP_LP_UNIT)
-#error "the obstacle units are link-position units"
-#endif
-#if defined(FR_COOP_CAP_UNIT) && !defined(FR_COOP_OB_UNIT)
-#error "the capsule units are obstacle units"
-#endif
-#if defined(FR_COOP_DF_UNIT) && !defined(FR_COOP_CAP_UNIT)
-#error "the distance-field units are capsule units"
-#endif
-#if defined(FR_COOP_DF_UNIT)
-#define FR_UNIT_OB OB_TERM_FIELD
-#elif defined(FR_COOP_CAP_UNIT)
-#define FR_UNIT_OB OB_TERM_CAPSULES
-#elif defined(FR_COOP_OB_UNIT)
-#define FR_UNIT_OB OB_TERM_POINTS
-#else
-#define FR_UNIT_OB OB_TERM_NONE
-#endif
-
 #ifdef PHASE_MARKS
 #define PMARK(n) asm volatile("; PHASE " #n)
 #define PMARK_D(n, x) asm volatile("; PHASE " #n : "+v"(x))
@@ -142,7 +139,8 @@ static_assert(LDS_KIN % 32 == 16 && LDS_SCR % 32 == 16 && LDS_KIN_EN % 32 == 16,
 // velocity weight of the cost, and the lane masks of the kinematic sums.  Row 12 serves lanes
 // 12..15: body 0's geometry with every mask and weight zero.
 constexpr int T_R = 0, T_P = 9, T_M = 12, T_C = 13, T_IA = 16, T_IB = 19, T_F = 22, T_MA = 25, T_AX = 28, T_ROT = 31, T_NROT = 32;
-constexpr int T_LO = 33, T_UP = 36, T_VW = 39, T_WV = 40, T_WA = 41, T_FIX = 42, T_MC = 43, T_IL = 44;
+// (maybe_unused: some are the table kernel's alone, which only the default unit has)
+[[maybe_unused]] constexpr int T_LO = 33, T_UP = 36, T_VW = 39, T_WV = 40, T_WA = 41, T_FIX = 42, T_MC = 43, T_IL = 44;
 constexpr int MB = 45;   // odd: lanes reading their own body's entry hit distinct banks
 constexpr int LDS_MODEL = (FR_NB + 1) * MB;
 static_assert(LDS_MODEL <= FR_BODY_TABLE, "body table buffer");
@@ -1048,7 +1046,7 @@ __device__ __forceinline__ void composite_scan(double *v, const double *m)
     // (no leading s_nop: tools/dpp_hazard_check.py checks every build that the lanes' own (h, Ib),
     // the DPP sources, were not written in the two instructions before the block; the simulated
     // wrench's units, where the compiler places the products h = m c right ahead of it, lead with one)
-#ifdef FR_COOP_WR_UNIT
+#if FR_UNIT_WR
 #define COMPOSITE_SCAN_LEAD "s_nop 1\n\t"
 #else
 #define COMPOSITE_SCAN_LEAD ""
@@ -1236,7 +1234,7 @@ __device__ __forceinline__ double coop_solve(int j, const LaneConst &L, const Co
 // Jacobi rotations to its eigenvalues / vectors, l the least eigenvalue, a and b the other two
 // eigenvectors times sqrt(lambda - l) (inertias are positive semi-definite, so l >= 0 and the two
 // excesses are >= 0; rounding is clamped).
-#ifndef FR_COOP_VARIANT_UNIT   // (the table kernel lives in the main unit alone)
+#if FR_UNIT_DEFAULT   // (the table kernel lives in the default unit alone)
 __device__ void inertia_rank2(const double *Ic, double *a, double *b, double *l)
 {
     double A[3][3] = {{Ic[0], Ic[1], Ic[3]}, {Ic[1], Ic[2], Ic[4]}, {Ic[3], Ic[4], Ic[5]}};
@@ -1330,7 +1328,7 @@ __global__ void fr_body_table_kernel(const DevModel *model, const DevCost *cost,
         table[t] = v;
     }
 }
-#endif   // FR_COOP_VARIANT_UNIT
+#endif   // FR_UNIT_DEFAULT
 
 // Stage the body table in LDS.
 __device__ __forceinline__ void stage_body_table(const FrRolloutArgs &a, double *Lmodel, int nt)
@@ -1727,8 +1725,8 @@ __device__ __forceinline__ void launch_row_cost(const FrRolloutArgs &a, int64_t 
     if (!(lr < a.count || frow)) return;
     if (frow && (a.status->all_nan || a.status->sg_error)) return;   // no filter() when the update threw
     double J;
-    if constexpr (LP && FR_UNIT_OB)   // (the row's table: behind the step constants it reads)
-        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true, FR_UNIT_OB>(*a.cost, frow ? a.fsteps : a.steps,
+    if constexpr (LP && UNIT_OB)   // (the row's table: behind the step constants it reads)
+        J = mppi_cost::rollout_cost<CK, EN, MB, KC, true, UNIT_OB>(*a.cost, frow ? a.fsteps : a.steps,
                                                                  frow ? a.frec : a.rec + lr * a.H * (KC ? FR_REC_C : FR_REC), a.H,
                                                                  lane, Lmodel + T_LO, mppi_cost::LinkModel{a.model, a.dt});
     else if constexpr (LP)
@@ -2036,14 +2034,14 @@ __device__ __forceinline__ void cost_chunk(const FrRolloutArgs &a, int g, int c,
     const ChunkLane L = chunk_lane(a, g, c, lane);
     PMARK(8);
     double cs;
-    if constexpr (LP && FR_UNIT_OB) {
+    if constexpr (LP && UNIT_OB) {
         // the relay group's chunks hold the folded filter() row beside this update's rows: that row's
         // lanes read the previous update's table (ObstacleRef: a second pass, in such a wave only)
         const bool frow = a.fcost != nullptr && group_row0(a, g) + (lane >> 4) == a.count;
         const bool anyf = __builtin_amdgcn_ballot_w64(frow) != 0;
         const mppi_cost::ObstacleRef ob{mppi_cost::obstacle_table_of(a.steps, a.H),
                                         anyf ? mppi_cost::obstacle_table_of(a.fsteps, a.H) : nullptr, frow, L.kk};
-        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true, FR_UNIT_OB>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
+        cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true, UNIT_OB>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
                                                                            mppi_cost::LinkModel{a.model, a.dt}, L.kk == 0, ob);
     } else if constexpr (LP)
         cs = mppi_cost::record_step_cost<CK, EN, MB, false, 2, true>(*a.cost, *L.stp, L.rec, Lmodel + T_LO,
@@ -2318,73 +2316,28 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 // on the free CU (per-block traces, tools/wave_trace.py).
 // KC: compact records with the kinematic sums on the rows' chains (the update's launches, throughput-
 // bound); the standalone filter() row (one latency-bound row) keeps the 768-B record and a shorter step.
-// LP: the objective of the kinematic link-position model (FrRolloutArgs::link_positions).  The
-// kernels' body is shared text (fr_coop_kernel_body.inc, fr_coop_x_kernel_body.inc); the LP = true
-// versions are kernels of their own (fr_coop_lp_kernel, fr_coop_x_lp_kernel) in a translation unit
-// of their own (fr_coop_lp.hip, which includes this file with FR_COOP_LP_UNIT): in one unit with the
-// default mode's kernels they changed fr_coop_x_kernel's scalar code, and apart the default mode's
-// are the same functions, by name and by instruction.
-// WR: the simulated end-effector wrench in the step (FrRolloutArgs::simulated_wrench, coop_rows),
-// again kernels and units of their own (fr_coop_wr.hip; with LP, fr_coop_wr_lp.hip).
-// OB: the obstacle term in the LP objective (FrRolloutArgs::link_positions == 2), units
-// fr_coop_lp_ob.hip and fr_coop_wr_lp_ob.hip; with segments and capsule obstacles (== 3), units
-// fr_coop_lp_cap.hip and fr_coop_wr_lp_cap.hip; with the distance field (== 4), units fr_coop_lp_df.hip
-// and fr_coop_wr_lp_df.hip.
-#if defined(FR_COOP_DF_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_COOP_K fr_coop_wr_lp_df_kernel
-#define FR_COOP_XK fr_coop_x_wr_lp_df_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR true
-#elif defined(FR_COOP_DF_UNIT)
-#define FR_COOP_K fr_coop_lp_df_kernel
-#define FR_COOP_XK fr_coop_x_lp_df_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR false
-#elif defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_COOP_K fr_coop_wr_lp_cap_kernel
-#define FR_COOP_XK fr_coop_x_wr_lp_cap_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR true
-#elif defined(FR_COOP_CAP_UNIT)
-#define FR_COOP_K fr_coop_lp_cap_kernel
-#define FR_COOP_XK fr_coop_x_lp_cap_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR false
-#elif defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_COOP_K fr_coop_wr_lp_ob_kernel
-#define FR_COOP_XK fr_coop_x_wr_lp_ob_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR true
-#elif defined(FR_COOP_OB_UNIT)
-#define FR_COOP_K fr_coop_lp_ob_kernel
-#define FR_COOP_XK fr_coop_x_lp_ob_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR false
-#elif defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
-#define FR_COOP_K fr_coop_wr_lp_kernel
-#define FR_COOP_XK fr_coop_x_wr_lp_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR true
-#elif defined(FR_COOP_WR_UNIT)
-#define FR_COOP_K fr_coop_wr_kernel
-#define FR_COOP_XK fr_coop_x_wr_kernel
-#define FR_UNIT_LP false
-#define FR_UNIT_WR true
-#elif defined(FR_COOP_LP_UNIT)
-#define FR_COOP_K fr_coop_lp_kernel
-#define FR_COOP_XK fr_coop_x_lp_kernel
-#define FR_UNIT_LP true
-#define FR_UNIT_WR false
-#else
-#define FR_COOP_K fr_coop_kernel
-#define FR_COOP_XK fr_coop_x_kernel
-#define FR_UNIT_LP false
-#define FR_UNIT_WR false
-#endif
+// LP, WR: the unit's cell (the top of this file).  The kernels' body is shared text
+// (fr_coop_kernel_body.inc, fr_coop_x_kernel_body.inc); the cell is in the kernels' names, not in their
+// template arguments, so that profiles and traces tell the units apart by name.  The name is pasted from
+// the cell's two tags: fr_coop_ or fr_coop_x_, the wrench's, the link mode's, kernel.
+#define FR_WR_TAG_0
+#define FR_WR_TAG_1 wr_
+#define FR_LINKS_TAG_0
+#define FR_LINKS_TAG_1 lp_
+#define FR_LINKS_TAG_2 lp_ob_
+#define FR_LINKS_TAG_3 lp_cap_
+#define FR_LINKS_TAG_4 lp_df_
+#define FR_PASTE2_(a, b) a##b
+#define FR_PASTE2(a, b) FR_PASTE2_(a, b)
+#define FR_PASTE4_(a, b, c, d) a##b##c##d
+#define FR_PASTE4(a, b, c, d) FR_PASTE4_(a, b, c, d)
+#define FR_UNIT_KERNEL(stem) FR_PASTE4(stem, FR_PASTE2(FR_WR_TAG_, FR_UNIT_WR), FR_PASTE2(FR_LINKS_TAG_, FR_UNIT_LINKS), kernel)
+#define FR_COOP_K FR_UNIT_KERNEL(fr_coop_)
+#define FR_COOP_XK FR_UNIT_KERNEL(fr_coop_x_)
 template <int CK, bool EN, int WPB, bool KC>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void FR_COOP_K(FrRolloutArgs a)
 {
-    constexpr bool LP = FR_UNIT_LP, WR = FR_UNIT_WR;
+    constexpr bool LP = UNIT_LP, WR = UNIT_WR;
 #include "fr_coop_kernel_body.inc"
 }
 
@@ -2398,7 +2351,7 @@ constexpr int XW = 8;
 template <int CK, bool EN>
 __global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, 2))) void FR_COOP_XK(FrRolloutArgs a)
 {
-    constexpr bool LP = FR_UNIT_LP, WR = FR_UNIT_WR;
+    constexpr bool LP = UNIT_LP, WR = UNIT_WR;
 #include "fr_coop_x_kernel_body.inc"
 }
 
@@ -2417,23 +2370,16 @@ static unsigned one_per_cu_pad(K kernel, int wpb)
     return at.sharedSizeBytes >= want ? 0u : (unsigned)(want - at.sharedSizeBytes);
 }
 
-// The variant units' launches (fr_coop_lp.hip, fr_coop_wr.hip, fr_coop_wr_lp.hip and the two obstacle
-// units): the x kernel, and
-// the unit's fr_coop_*_kernel with wpb waves per workgroup and compact or 768-B records
-#define FR_UNIT_DECL(tag)                                                                                     \
-    void launch_fr_coop_##tag##_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);                        \
-    void launch_fr_coop_##tag##_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact); \
-    bool fr_coop_##tag##_is_update_kernel(const void *func);   /* an x-kernel instantiation of the unit */
-FR_UNIT_DECL(lp)
-FR_UNIT_DECL(wr)
-FR_UNIT_DECL(wr_lp)
-FR_UNIT_DECL(lp_ob)
-FR_UNIT_DECL(wr_lp_ob)
-FR_UNIT_DECL(lp_cap)
-FR_UNIT_DECL(wr_lp_cap)
-FR_UNIT_DECL(lp_df)
-FR_UNIT_DECL(wr_lp_df)
-#undef FR_UNIT_DECL
+// What a unit gives the host: the launch of its x kernel, the launch of its fr_coop_*_kernel with wpb
+// waves per workgroup and compact or 768-B records, and whether a function is one of its x kernels.
+// Declared here for the whole grid; every unit defines the members of its own cell below, so a unit
+// that is not built is an undefined symbol when the library is linked.
+template <int LINKS, bool WR>
+struct FrCoopUnit {
+    static void x(const FrRolloutArgs &a, unsigned nb, hipStream_t s);
+    static void one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact);
+    static bool is_update_kernel(const void *func);
+};
 
 template <int CK, bool EN, int WPB, bool KC>
 static void launch_k(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
@@ -2452,71 +2398,61 @@ static void launch_x(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 template <int WPB, bool KC>
 static void launch_one(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-#ifndef FR_COOP_VARIANT_UNIT
-    if (a.link_positions == FR_LINKS_FIELD)
-        return a.simulated_wrench ? launch_fr_coop_wr_lp_df_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_df_one(a, nb, s, WPB, KC);
-    if (a.link_positions == FR_LINKS_CAPSULES)
-        return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_cap_one(a, nb, s, WPB, KC);
-    if (a.link_positions == FR_LINKS_OBSTACLES)
-        return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_one(a, nb, s, WPB, KC) : launch_fr_coop_lp_ob_one(a, nb, s, WPB, KC);
-    if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_one(a, nb, s, WPB, KC) : launch_fr_coop_wr_one(a, nb, s, WPB, KC);
-    if (a.link_positions) return launch_fr_coop_lp_one(a, nb, s, WPB, KC);
-#endif
     if (a.cost_kind == CK_TRACK_POINT) launch_k<CK_TRACK_POINT, false, WPB, KC>(a, nb, s);
     else if (a.energy) launch_k<CK_ASSISTED_MANIPULATION, true, WPB, KC>(a, nb, s);
     else launch_k<CK_ASSISTED_MANIPULATION, false, WPB, KC>(a, nb, s);
 }
 
-static void launch_x_any(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
+using ThisUnit = FrCoopUnit<FR_UNIT_LINKS, UNIT_WR>;
+
+template <>
+void ThisUnit::x(const FrRolloutArgs &a, unsigned nb, hipStream_t s)
 {
-#ifndef FR_COOP_VARIANT_UNIT
-    if (a.link_positions == FR_LINKS_FIELD) return a.simulated_wrench ? launch_fr_coop_wr_lp_df_x(a, nb, s) : launch_fr_coop_lp_df_x(a, nb, s);
-    if (a.link_positions == FR_LINKS_CAPSULES) return a.simulated_wrench ? launch_fr_coop_wr_lp_cap_x(a, nb, s) : launch_fr_coop_lp_cap_x(a, nb, s);
-    if (a.link_positions == FR_LINKS_OBSTACLES) return a.simulated_wrench ? launch_fr_coop_wr_lp_ob_x(a, nb, s) : launch_fr_coop_lp_ob_x(a, nb, s);
-    if (a.simulated_wrench) return a.link_positions ? launch_fr_coop_wr_lp_x(a, nb, s) : launch_fr_coop_wr_x(a, nb, s);
-    if (a.link_positions) return launch_fr_coop_lp_x(a, nb, s);
-#endif
     if (a.cost_kind == CK_TRACK_POINT) launch_x<CK_TRACK_POINT, false>(a, nb, s);
     else if (a.energy) launch_x<CK_ASSISTED_MANIPULATION, true>(a, nb, s);
     else launch_x<CK_ASSISTED_MANIPULATION, false>(a, nb, s);
 }
 
-#ifdef FR_COOP_VARIANT_UNIT
-#if defined(FR_COOP_DF_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_UNIT_FN(pre, post) pre##wr_lp_df##post
-#elif defined(FR_COOP_DF_UNIT)
-#define FR_UNIT_FN(pre, post) pre##lp_df##post
-#elif defined(FR_COOP_CAP_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_UNIT_FN(pre, post) pre##wr_lp_cap##post
-#elif defined(FR_COOP_CAP_UNIT)
-#define FR_UNIT_FN(pre, post) pre##lp_cap##post
-#elif defined(FR_COOP_OB_UNIT) && defined(FR_COOP_WR_UNIT)
-#define FR_UNIT_FN(pre, post) pre##wr_lp_ob##post
-#elif defined(FR_COOP_OB_UNIT)
-#define FR_UNIT_FN(pre, post) pre##lp_ob##post
-#elif defined(FR_COOP_WR_UNIT) && defined(FR_COOP_LP_UNIT)
-#define FR_UNIT_FN(pre, post) pre##wr_lp##post
-#elif defined(FR_COOP_WR_UNIT)
-#define FR_UNIT_FN(pre, post) pre##wr##post
-#else
-#define FR_UNIT_FN(pre, post) pre##lp##post
-#endif
-void FR_UNIT_FN(launch_fr_coop_, _x)(const FrRolloutArgs &a, unsigned nb, hipStream_t s) { launch_x_any(a, nb, s); }
-
-void FR_UNIT_FN(launch_fr_coop_, _one)(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact)
+template <>
+void ThisUnit::one(const FrRolloutArgs &a, unsigned nb, hipStream_t s, int wpb, bool compact)
 {
     if (wpb == 4) launch_one<4, true>(a, nb, s);   // (the four-wave launch writes compact records only)
     else if (compact) launch_one<1, true>(a, nb, s);
     else launch_one<1, false>(a, nb, s);
 }
 
-bool FR_UNIT_FN(fr_coop_, _is_update_kernel)(const void *f)
+template <>
+bool ThisUnit::is_update_kernel(const void *f)
 {
     return f == (const void *)&FR_COOP_XK<CK_ASSISTED_MANIPULATION, false> ||
            f == (const void *)&FR_COOP_XK<CK_ASSISTED_MANIPULATION, true> ||
            f == (const void *)&FR_COOP_XK<CK_TRACK_POINT, false>;
 }
-#else
+
+#if FR_UNIT_DEFAULT
+// The grid of units, [link mode][wrench]: made from the grid's bounds, so there is no list to keep.
+struct UnitEntry {
+    decltype(&ThisUnit::x) x;
+    decltype(&ThisUnit::one) one;
+    decltype(&ThisUnit::is_update_kernel) is_update_kernel;
+};
+template <int LINKS, bool WR>
+constexpr UnitEntry unit_entry() { return {&FrCoopUnit<LINKS, WR>::x, &FrCoopUnit<LINKS, WR>::one, &FrCoopUnit<LINKS, WR>::is_update_kernel}; }
+template <int... LINKS>
+constexpr std::array<std::array<UnitEntry, 2>, sizeof...(LINKS)> unit_table(std::integer_sequence<int, LINKS...>)
+{
+    return {{{{unit_entry<LINKS, false>(), unit_entry<LINKS, true>()}}...}};
+}
+constexpr auto UNITS = unit_table(std::make_integer_sequence<int, FR_LINKS_FIELD + 1>{});
+
+// The launch's unit.  The engine passes FR_LINKS_ZERO .. FR_LINKS_FIELD (engine.cpp launch_link_mode);
+// any other value means the link-position objective alone, as every non-zero value short of an obstacle
+// mode does, and never indexes the table.
+static const UnitEntry &unit_of(const FrRolloutArgs &a)
+{
+    const int links = a.link_positions >= FR_LINKS_ZERO && a.link_positions <= FR_LINKS_FIELD ? a.link_positions : FR_LINKS_KINEMATIC;
+    return UNITS[links][a.simulated_wrench != 0];
+}
 
 bool fr_coop_compact(const FrRolloutArgs &a) { return !a.optimal; }
 
@@ -2524,8 +2460,7 @@ hipError_t launch_fr_coop(const FrRolloutArgs &a, hipStream_t s)
 {
     const unsigned nb = (unsigned)((a.count + ROWS_PER_WAVE - 1) / ROWS_PER_WAVE);
     if (nb == 0) return hipSuccess;
-    if (fr_coop_compact(a)) launch_one<1, true>(a, nb, s);
-    else launch_one<1, false>(a, nb, s);   // the standalone filter() row
+    unit_of(a).one(a, nb, s, 1, fr_coop_compact(a));   // (not compact: the standalone filter() row)
     return hipGetLastError();
 }
 
@@ -2543,12 +2478,10 @@ bool fr_coop_costs_in_launch(const EnvSwitches &env) { return !env.costs_in_laun
 
 bool fr_coop_is_update_kernel(const void *f)
 {
-    return f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, false> ||
-           f == (const void *)&fr_coop_x_kernel<CK_ASSISTED_MANIPULATION, true> ||
-           f == (const void *)&fr_coop_x_kernel<CK_TRACK_POINT, false> || fr_coop_lp_is_update_kernel(f) ||
-           fr_coop_wr_is_update_kernel(f) || fr_coop_wr_lp_is_update_kernel(f) || fr_coop_lp_ob_is_update_kernel(f) ||
-           fr_coop_wr_lp_ob_is_update_kernel(f) || fr_coop_lp_cap_is_update_kernel(f) || fr_coop_wr_lp_cap_is_update_kernel(f) ||
-           fr_coop_lp_df_is_update_kernel(f) || fr_coop_wr_lp_df_is_update_kernel(f);
+    for (const auto &mode : UNITS)
+        for (const UnitEntry &u : mode)
+            if (u.is_update_kernel(f)) return true;
+    return false;
 }
 
 // The arguments of a launch over rows [r0, r0 + n) of `a`'s shard: the row-indexed buffers start at
@@ -2591,17 +2524,18 @@ hipError_t launch_fr_coop_update(const FrRolloutArgs &a, const CoopPlan &p, hipS
 {
     if (p.error) return hipErrorInvalidValue;
     if (e0) (void)hipEventRecord(e0, s);
+    const UnitEntry &u = unit_of(a);
     for (int i = 0; i < p.nlaunch; i++) {
         const CoopLaunch &l = p.l[i];
         const FrRolloutArgs b = fr_coop_launch_args(a, p, i);
-        if (l.kind == COOP_X) launch_x_any(b, l.grid, s);
-        else if (l.kind == COOP_FOUR_WAVE) launch_one<4, true>(b, l.grid, s);
-        else if (l.grid) launch_one<1, true>(b, l.grid, s);
+        if (l.kind == COOP_X) u.x(b, l.grid, s);
+        else if (l.kind == COOP_FOUR_WAVE) u.one(b, l.grid, s, 4, true);
+        else if (l.grid) u.one(b, l.grid, s, 1, true);
     }
     if (e1) (void)hipEventRecord(e1, s);
     return hipGetLastError();
 }
 
-#endif   // FR_COOP_VARIANT_UNIT
+#endif   // FR_UNIT_DEFAULT
 
 }  // namespace mppi_eng
