@@ -22,6 +22,7 @@ from .obstacles import (CapsuleObstacle, HalfSpaceObstacle, ObstacleAvoidance, O
                         MASK_ALL, MASK_SEGMENTS, mask_segment, obstacle_clearance, obstacle_from_c, obstacles_to_c,
                         segment_distance)
 from .distance_field import DistanceField, field_clearance  # noqa: E402
+from .targets import TargetPath, TargetTracking, quaternion_rotation  # noqa: E402
 from .safety import TrajectorySafetyFilter  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
 from .dynamics import DynamicsForecast, EndEffectorState, PinocchioDynamicsObject, evaluate_cost  # noqa: E402
@@ -35,4 +36,5 @@ __all__ = [
     "comm_unique_id", "shard_range", "Predicted", "ObstacleAvoidance", "SphereObstacle", "HalfSpaceObstacle",
     "obstacle_clearance", "TrajectorySafetyFilter", "CapsuleObstacle", "ObstacleCapsules", "MASK_ALL", "MASK_SEGMENTS",
     "mask_segment", "obstacle_from_c", "obstacles_to_c", "segment_distance", "DistanceField", "field_clearance",
+    "TargetPath", "TargetTracking", "quaternion_rotation",
 ]

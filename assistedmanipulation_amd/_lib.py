@@ -122,6 +122,13 @@ PROTOTYPES = {
     "mppi_set_distance_field": (C.c_int, [_h, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float)]),
     "mppi_get_distance_field": (C.c_int, [_h, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_int)]),
     "mppi_optimal_field_cost": (C.c_int, [_h, _dp]),
+    "mppi_default_target_tracking_config": (None, [C.POINTER(abi.mppi_target_tracking_config)]),
+    "mppi_set_target_tracking": (C.c_int, [_h, C.POINTER(abi.mppi_target_tracking_config)]),
+    "mppi_get_target_tracking": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(abi.mppi_target_tracking_config)]),
+    "mppi_set_target_path": (C.c_int, [_h, C.POINTER(abi.mppi_target_path)]),
+    "mppi_get_target_path": (C.c_int, [_h, C.POINTER(abi.mppi_target_path), C.POINTER(C.c_int)]),
+    "mppi_optimal_target_cost": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_target_cost": (C.c_int, [_h, _dp, _dp, C.POINTER(abi.mppi_target_tracking_config), _dp]),
     "mppi_dynamics_distance_field_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_capsule_config),
                                                     C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float), _dp]),
 }

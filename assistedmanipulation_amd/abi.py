@@ -179,6 +179,23 @@ class mppi_capsule_config(C.Structure):
     _fields_ = [("segment_radii", _d * MPPI_OBSTACLE_SEGMENTS)]
 
 
+# mppi_set_target_tracking / mppi_set_target_path
+MPPI_TARGET_WAYPOINTS_MAX = 32
+
+
+class mppi_target_tracking_config(C.Structure):
+    _fields_ = [("orientation_weight", _d), ("track_orientation", C.c_int32)]
+
+
+class mppi_target_waypoint(C.Structure):
+    _fields_ = [("time", _d), ("position", _d * 3), ("quaternion", _d * 4)]
+
+
+class mppi_target_path(C.Structure):
+    _fields_ = [("count", C.c_int32), ("has_orientation", C.c_int32),
+                ("waypoints", mppi_target_waypoint * MPPI_TARGET_WAYPOINTS_MAX)]
+
+
 # mppi_set_distance_field
 MPPI_DISTANCE_FIELD_MIN_DIM = 2
 MPPI_DISTANCE_FIELD_MAX_DIM = 512

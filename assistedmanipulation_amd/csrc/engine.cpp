@@ -372,6 +372,17 @@ struct mppi_handle {
     // (FR_LINKS_CAPSULES), fixed once enabled like avoidance itself
     bool obstacle_capsules = false;
     mppi_capsule_config cap_config{};
+    // mppi_set_target_tracking / mppi_set_target_path (TrackPoint): the configuration (fixed once
+    // enabled, before the first update) and the current path as stored - quaternions normalised and
+    // sign-fixed, tp_inv[i] = 1 / (time[i + 1] - time[i]).  Each update samples it at its own times into
+    // the target fields of its step constants (write_target_table; StepTarget), so the buffers alternate
+    // as for the wrench rows; the hipGraph path launches that ahead of the graph, like them.
+    bool target_tracking = false;
+    mppi_target_tracking_config tt_config{};
+    bool tp_present = false;
+    mppi_target_path tp_path{};
+    double tp_inv[MPPI_TARGET_WAYPOINTS_MAX] = {};
+    double tp_point[3] = {0, 0, 0};   // the descriptor's point: the target without a path
     // mppi_set_distance_field_avoidance: the field kernels (FR_LINKS_FIELD), fixed once enabled.
     // mppi_set_distance_field: the descriptor and two device grids.  A set writes the grid that the
     // last update's table does not reference (field_last; -1: none), behind the stream's earlier
@@ -1207,6 +1218,39 @@ mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_co
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_target_cost(mppi_dynamics *d, const double *point3, const double *quaternion4,
+                                      const mppi_target_tracking_config *config, double *out2)
+{
+    if (!d || !point3 || !out2) return MPPI_ERR_INVALID;
+    mppi_target_tracking_config c;
+    if (config) c = *config;
+    else mppi_default_target_tracking_config(&c);
+    if (!std::isfinite(c.orientation_weight) || c.orientation_weight < 0.0)
+        return dfail(d, MPPI_ERR_INVALID, "target cost: orientation_weight must be finite and >= 0");
+    ObjTarget t{};
+    for (int i = 0; i < 3; i++) {
+        if (!std::isfinite(point3[i])) return dfail(d, MPPI_ERR_INVALID, "target cost: the point must be finite");
+        t.point[i] = point3[i];
+    }
+    t.w = c.orientation_weight;
+    if (quaternion4) {
+        const double *q = quaternion4;
+        for (int i = 0; i < 4; i++)
+            if (!std::isfinite(q[i])) return dfail(d, MPPI_ERR_INVALID, "target cost: the quaternion must be finite");
+        const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+        if (!(n >= 0.5 && n <= 2.0)) return dfail(d, MPPI_ERR_INVALID, "target cost: the quaternion's norm must be in [0.5, 2]");
+        for (int i = 0; i < 4; i++) t.q[i] = q[i] / n;
+        t.has_q = 1;
+    }
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(launch_fr_object_target(d->d_obj, t, d->d_buf, d->stream));
+    DHIP_TRY(hipMemcpyAsync(out2, d->d_buf, 2 * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipStreamSynchronize(d->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_capsule_config *capsules,
                                        const mppi_obstacle *obstacles, int32_t count, double elapsed, double *cost)
 {
@@ -1434,6 +1478,7 @@ mppi_status mppi_create(const mppi_config *cfg, const mppi_dynamics_desc *dyn, c
     h->sg_window = cfg->has_smoothing ? (int)cfg->smoothing_window : 0;
     h->sg_order = cfg->has_smoothing ? (int)cfg->smoothing_order : 0;
     h->am = cost->assisted_manipulation;
+    for (int i = 0; i < 3; i++) h->tp_point[i] = cost->track_point.point[i];
     h->quad = cost->quadratic;
     h->pm_mass = dyn->point_mass.mass;
     h->begin = 0;
@@ -1840,6 +1885,8 @@ mppi_status mppi_forecast_attach(mppi_handle *h, const mppi_forecast_config *c)
         f.type = FC_NONE;
         return upload_steps(h);
     }
+    // (the forecast's step constants are written whole, over the fields a tracking handle's targets live in)
+    if (h->target_tracking) return fail(h, MPPI_ERR_INVALID, "forecast attach: target tracking is enabled (mppi_set_target_tracking)");
     // Forecast::create (forecast.cpp:6-39) and the kind's create()
     if (c->type != MPPI_FORECAST_LOCF && c->type != MPPI_FORECAST_AVERAGE && c->type != MPPI_FORECAST_KALMAN)
         return fail(h, MPPI_ERR_INVALID, "unknown forecast type " + std::to_string(c->type) + "selected");
@@ -2134,6 +2181,32 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
     return MPPI_OK;
 }
 
+// This update's targets, in the target fields of its step constants (StepTarget): the path as it
+// stands, sampled at time + k dt.  The path changes between updates and the times with every update,
+// so the buffers alternate as they do for the wrench rows: the pending filter() of the previous update
+// reads the other one.  One small launch on the engine stream ahead of the rollouts, the path by value.
+static mppi_status write_target_table(mppi_handle *h, double time)
+{
+    h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
+    TargetPathArgs a{};
+    a.n = h->tp_present ? h->tp_path.count : 0;
+    a.has_q = h->tp_present && h->tp_path.has_orientation ? 1 : 0;
+    a.H = (int)h->H;
+    a.t0 = time;
+    a.dt = h->dt;
+    for (int c = 0; c < 3; c++) a.point[c] = h->tp_point[c];
+    for (int i = 0; i < a.n; i++) {
+        const mppi_target_waypoint &w = h->tp_path.waypoints[i];
+        a.time[i] = w.time;
+        a.inv[i] = h->tp_inv[i];
+        for (int c = 0; c < 3; c++) a.p[i][c] = w.position[c];
+        for (int c = 0; c < 4; c++) a.q[i][c] = w.quaternion[c];
+    }
+    a.out = h->d_steps;
+    HIP_TRY(launch_target_table(a, h->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
 {
     if (!h || !state) return MPPI_ERR_INVALID;
@@ -2156,6 +2229,10 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
     }
     if (h->obstacle_avoidance && !h->wrench_ahead) {
         mppi_status st = write_obstacle_table(h, time);
+        if (st != MPPI_OK) return st;
+    }
+    if (h->target_tracking && !h->wrench_ahead) {
+        mppi_status st = write_target_table(h, time);
         if (st != MPPI_OK) return st;
     }
 
@@ -2748,6 +2825,11 @@ static mppi_status update_graph(mppi_handle *h, const double *state, double time
         mppi_status ws = write_obstacle_table(h, time);
         if (ws != MPPI_OK) return ws;
     }
+    // and the targets of a tracking handle: the current path at this update's times
+    if (h->target_tracking) {
+        mppi_status ws = write_target_table(h, time);
+        if (ws != MPPI_OK) return ws;
+    }
     if (capture) HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     else h->graph_dry = true;
     h->wrench_ahead = true;
@@ -2856,6 +2938,8 @@ mppi_status mppi_set_link_positions(mppi_handle *h, int mode)
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "the link-position model is set before the first update");
     if (h->obstacle_avoidance && mode != MPPI_LINK_POSITIONS_KINEMATIC)
         return fail(h, MPPI_ERR_INVALID, "obstacle avoidance is enabled: the link-position model stays MPPI_LINK_POSITIONS_KINEMATIC");
+    if (h->target_tracking && h->tt_config.track_orientation && mode != MPPI_LINK_POSITIONS_KINEMATIC)
+        return fail(h, MPPI_ERR_INVALID, "orientation tracking is enabled: the link-position model stays MPPI_LINK_POSITIONS_KINEMATIC");
     h->link_positions = mode;
     return MPPI_OK;
 }
@@ -3423,6 +3507,127 @@ mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, (h->field_avoidance ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->field_avoidance ? h->h_opt[1] + h->h_opt[2] : h->h_opt[1];
+    return MPPI_OK;
+}
+
+void mppi_default_target_tracking_config(mppi_target_tracking_config *out)
+{
+    if (!out) return;
+    *out = mppi_target_tracking_config{};
+    out->orientation_weight = 10.0;
+    out->track_orientation = 0;
+}
+
+mppi_status mppi_set_target_tracking(mppi_handle *h, const mppi_target_tracking_config *config)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK || h->cost_kind != MPPI_COST_TRACK_POINT)
+        return fail(h, MPPI_ERR_UNSUPPORTED, "target tracking: FrankaRidgeback handles with the TrackPoint objective only");
+    // the targets' launch is part of the update path and ahead of a captured graph from the first update on
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "target tracking is enabled before the first update");
+    if (h->fc.type != FC_NONE)
+        return fail(h, MPPI_ERR_INVALID, "target tracking: a forecast is attached (mppi_forecast_attach), whose step constants take the targets' place");
+    mppi_target_tracking_config c;
+    if (config) c = *config;
+    else mppi_default_target_tracking_config(&c);
+    if (!std::isfinite(c.orientation_weight) || c.orientation_weight < 0.0)
+        return fail(h, MPPI_ERR_INVALID, "target tracking: orientation_weight must be finite and >= 0");
+    if (c.track_orientation != 0 && c.track_orientation != 1)
+        return fail(h, MPPI_ERR_INVALID, "target tracking: track_orientation must be 0 or 1");
+    if (c.track_orientation && h->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return fail(h, MPPI_ERR_INVALID, "target tracking: track_orientation needs the kinematic link-position model (mppi_set_link_positions)");
+    HIP_TRY(hipSetDevice(h->device));
+    // the objective's device block gains the switches (nothing has run yet: before the first update)
+    struct { int track, orient; double w; } sw = {1, c.track_orientation, c.orientation_weight};
+    static_assert(offsetof(DevCost, tp_track_orient) == offsetof(DevCost, tp_track) + sizeof(int) &&
+                  offsetof(DevCost, tp_orient_w) == offsetof(DevCost, tp_track) + 2 * sizeof(int), "the tracking switches are contiguous");
+    HIP_TRY(hipMemcpy(reinterpret_cast<char *>(h->d_cost) + offsetof(DevCost, tp_track), &sw, sizeof(sw), hipMemcpyHostToDevice));
+    h->tt_config = c;
+    h->target_tracking = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_target_tracking(mppi_handle *h, int *enabled, mppi_target_tracking_config *out)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->target_tracking ? 1 : 0;
+    if (h->target_tracking && out) *out = h->tt_config;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_target_path(mppi_handle *h, const mppi_target_path *path)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->target_tracking) return fail(h, MPPI_ERR_INVALID, "target path: target tracking is not enabled (mppi_set_target_tracking)");
+    if (!path) {
+        h->tp_present = false;
+        return MPPI_OK;
+    }
+    if (path->count < 1 || path->count > MPPI_TARGET_WAYPOINTS_MAX)
+        return fail(h, MPPI_ERR_INVALID, "target path: count must be in [1, " + std::to_string(MPPI_TARGET_WAYPOINTS_MAX) + "]");
+    mppi_target_path p{};
+    p.count = path->count;
+    p.has_orientation = path->has_orientation ? 1 : 0;
+    double inv[MPPI_TARGET_WAYPOINTS_MAX] = {};
+    for (int i = 0; i < p.count; i++) {
+        const mppi_target_waypoint &w = path->waypoints[i];
+        const std::string at = "target path: waypoint " + std::to_string(i) + ": ";
+        if (!std::isfinite(w.time)) return fail(h, MPPI_ERR_INVALID, at + "the time must be finite");
+        if (i > 0 && !(w.time > path->waypoints[i - 1].time)) return fail(h, MPPI_ERR_INVALID, at + "the times must be strictly increasing");
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(w.position[c])) return fail(h, MPPI_ERR_INVALID, at + "the position must be finite");
+        mppi_target_waypoint &o = p.waypoints[i];
+        o.time = w.time;
+        for (int c = 0; c < 3; c++) o.position[c] = w.position[c];
+        if (i > 0) {
+            inv[i - 1] = 1.0 / (w.time - path->waypoints[i - 1].time);
+            if (!std::isfinite(inv[i - 1])) return fail(h, MPPI_ERR_INVALID, at + "the time is too close to the waypoint before it");
+        }
+        if (!p.has_orientation) continue;
+        const double *q = w.quaternion;
+        for (int c = 0; c < 4; c++)
+            if (!std::isfinite(q[c])) return fail(h, MPPI_ERR_INVALID, at + "the quaternion must be finite");
+        const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+        if (!(n >= 0.5 && n <= 2.0)) return fail(h, MPPI_ERR_INVALID, at + "the quaternion's norm must be in [0.5, 2]");
+        for (int c = 0; c < 4; c++) o.quaternion[c] = q[c] / n;
+        if (i > 0) {   // the shorter way round from the waypoint before, as stored
+            const double *b = p.waypoints[i - 1].quaternion;
+            const double dot = ((b[0] * o.quaternion[0] + b[1] * o.quaternion[1]) + b[2] * o.quaternion[2]) + b[3] * o.quaternion[3];
+            if (dot < 0.0)
+                for (int c = 0; c < 4; c++) o.quaternion[c] = -o.quaternion[c];
+        }
+    }
+    h->tp_path = p;
+    for (int i = 0; i < MPPI_TARGET_WAYPOINTS_MAX; i++) h->tp_inv[i] = inv[i];
+    h->tp_present = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_target_path(mppi_handle *h, mppi_target_path *out, int *present)
+{
+    if (!h || !present) return MPPI_ERR_INVALID;
+    if (!h->target_tracking) return fail(h, MPPI_ERR_INVALID, "target path: target tracking is not enabled (mppi_set_target_tracking)");
+    *present = h->tp_present ? 1 : 0;
+    if (h->tp_present && out) *out = h->tp_path;
+    return MPPI_OK;
+}
+
+mppi_status mppi_optimal_target_cost(mppi_handle *h, double *out2)
+{
+    if (!h || !out2) return MPPI_ERR_INVALID;
+    if (!h->target_tracking) return fail(h, MPPI_ERR_UNSUPPORTED, "target cost: target tracking is not enabled");
+    HIP_TRY(hipSetDevice(h->device));
+    out2[0] = out2[1] = 0.0;
+    if (!h->published_once) return MPPI_OK;   // no filter() row yet
+    mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
+    if (st != MPPI_OK) return st;
+    // (the row's own update's targets: in opt_steps)
+    HIP_TRY(launch_fr_target_total(h->d_cost, h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact,
+                                   h->tt_config.track_orientation ? h->d_model : nullptr, h->dt, h->d_terms, h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    HIP_TRY(hipStreamSynchronize(h->stream_opt));
+    out2[0] = h->h_opt[1];
+    out2[1] = h->h_opt[2];
     return MPPI_OK;
 }
 

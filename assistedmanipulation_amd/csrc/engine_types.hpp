@@ -70,6 +70,12 @@ struct DevCost {
     // sphere links PIVOT, PANDA_LINK1..7 (radii[link - 3]).  Unread in the zero mode.
     DevBarrier sc_limit;
     double sc_radii[8];
+    // Target tracking (mppi_set_target_tracking, TrackPoint only; zeros otherwise): the step's target is
+    // read from its step constants (StepTarget) instead of tp_point, and with tp_track_orient the
+    // orientation term tp_orient_w (3 - sum_ij Rt_ij Ree_ij) follows the position term.  Behind
+    // everything the other kernels read: their offsets stay what they were.
+    int tp_track, tp_track_orient;
+    double tp_orient_w;
 };
 
 // FrankaRidgeback::Link (frankaridgeback/dynamics.hpp:65-80): the universe, then bodies 0..11.  The
@@ -88,6 +94,20 @@ struct StepConst {
     int active;         // has forecast && distance > threshold
     int pad;
 };
+
+// A tracking TrackPoint handle's view of a StepConst (mppi_set_target_tracking): the step's target
+// position and orientation (a unit quaternion x, y, z, w; all four 0: no orientation target) in the
+// trajectory-term fields, which TrackPoint kernels do not read; gamma_k stays where it is.  Written
+// per update by launch_target_table into the update's own step buffer.
+struct StepTarget {
+    double p[3];
+    double q[3];
+    double gamma_k;
+    double qw;
+};
+static_assert(sizeof(StepTarget) == sizeof(StepConst), "a StepConst seen as a target");
+static_assert(__builtin_offsetof(StepTarget, gamma_k) == __builtin_offsetof(StepConst, gamma_k), "gamma_k stays in place");
+constexpr int TARGET_WAYPOINTS_MAX = 32;
 
 // The obstacle set of one update (mppi_set_obstacle_avoidance, mppi_set_obstacles): the avoidance
 // configuration, the update's time t0 and the set's reference time, and up to OB_MAX obstacles.

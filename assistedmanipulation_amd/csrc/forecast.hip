@@ -270,9 +270,54 @@ __global__ __launch_bounds__(KT) void kalman_observe_kernel(DevKalman *__restric
     }
 }
 
+// The targets of an update's steps (mppi_set_target_path; kernels.hpp TargetPathArgs): step k samples
+// the path at t0 + k dt, the time get_cost is called with.  Every operation is rounded by itself, as
+// the host's sample writes it; the only divisions are by the interpolated quaternion's norm (>= sqrt(1/2)
+// after the host's sign fix), never by a time difference.  The waypoint index is bounded by n <= 32
+// whatever the times hold (a NaN time compares false everywhere: the loop ends at i = 0).
+__global__ __launch_bounds__(64) void target_table_kernel(TargetPathArgs a)
+{
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= a.H) return;
+    StepTarget *out = reinterpret_cast<StepTarget *>(a.out) + k;
+    double p[3] = {a.point[0], a.point[1], a.point[2]}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    const int n = a.n < TARGET_WAYPOINTS_MAX ? a.n : TARGET_WAYPOINTS_MAX;
+    if (n > 0) {
+        const double t = a.t0 + (double)k * a.dt;
+        int i = 0;
+        double f = 0.0;
+        if (t >= a.time[n - 1]) {
+            i = n - 1;
+        } else if (t > a.time[0]) {
+            for (int j = 1; j < n - 1; j++) i = (a.time[j] <= t) ? j : i;   // the greatest i with time[i] <= t
+            f = (t - a.time[i]) * a.inv[i];
+        }
+        const int i1 = (i + 1 < n) ? i + 1 : i;
+        for (int c = 0; c < 3; c++) p[c] = a.p[i][c] + f * (a.p[i1][c] - a.p[i][c]);
+        if (a.has_q) {
+            for (int c = 0; c < 4; c++) q[c] = a.q[i][c] + f * (a.q[i1][c] - a.q[i][c]);
+            const double nn = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+            for (int c = 0; c < 4; c++) q[c] = q[c] / nn;
+        }
+    }
+    for (int c = 0; c < 3; c++) {
+        out->p[c] = p[c];
+        out->q[c] = q[c];
+    }
+    out->qw = q[3];
+}
+
 }  // namespace
 
 namespace mppi_eng {
+
+hipError_t launch_target_table(const TargetPathArgs &a, hipStream_t s)
+{
+    if (a.H <= 0) return hipSuccess;
+    hipLaunchKernelGGL(target_table_kernel, dim3((unsigned)((a.H + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_forecast_steps(const ForecastArgs &f, const StepParams &p, const double *gamma, int H, double t0, double dt,
                                  StepConst *out, hipStream_t s)

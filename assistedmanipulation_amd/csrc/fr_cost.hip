@@ -144,6 +144,46 @@ __global__ __launch_bounds__(64) void fr_field_total_kernel(const StepConst *ste
     if (lane == 0) *out1 = tot;
 }
 
+// The target terms of the filter() row the same way (mppi_optimal_target_cost): the position term
+// 100 |p_EE - p(t_k)|^2 and the orientation term, each summed over the steps in step order,
+// undiscounted, with the targets of the row's own update (its step constants).  model: the kinematic
+// link-position model's, with the orientation switch on; else null and the orientation total is 0.
+__global__ __launch_bounds__(64) void fr_target_total_kernel(const DevCost *cost, const StepConst *steps, const double *rec, int H,
+                                                             int compact, const DevModel *model, double dt, double *out2)
+{
+    const int lane = threadIdx.x;
+    const DevCost &Cs = *cost;
+    double tp = 0.0, to = 0.0;
+    for (int base = 0; base < H; base += 64) {
+        const int n = (H - base < 64) ? H - base : 64;
+        const int k = base + (lane < n ? lane : 0);
+        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);   // (q, qd) pairs and the EE position: both layouts
+        const StepTarget *tg = reinterpret_cast<const StepTarget *>(steps + k);
+        const double *ee = r + REC_EE;
+        const bool track = Cs.tp_track != 0;
+        const double g0 = track ? tg->p[0] : Cs.tp_point[0], g1 = track ? tg->p[1] : Cs.tp_point[1], g2 = track ? tg->p[2] : Cs.tp_point[2];
+        const double d0 = ee[0] - g0, d1 = ee[1] - g1, d2 = ee[2] - g2;
+        const double distance = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        const double pt = 100.0 * (distance * distance);
+        double ot = 0.0;
+        if (model && track && Cs.tp_track_orient) {
+            double qj[10], lp[SC_LINKS][3], R9[9], Ree[9];
+            for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
+            link_fk(*model, qj, lp, R9);
+            grasp_rotation(R9, model->ee_R, Ree);
+            ot = target_orientation_term(Cs.tp_orient_w, tg->q[0], tg->q[1], tg->q[2], tg->qw, Ree);
+        }
+        for (int i = 0; i < n; i++) {
+            tp += readlane_f64(pt, i);
+            to += readlane_f64(ot, i);
+        }
+    }
+    if (lane == 0) {
+        out2[0] = tp;
+        out2[1] = to;
+    }
+}
+
 // The optimal rollout's per-term totals (AssistedManipulation's accumulators after filter(),
 // mppi.cpp:450-479 with thread 0's cost, reset at its start): one wave over the filter() row's
 // records, lane = step, each term summed over the steps in step order (m_*_cost += per step).
@@ -201,6 +241,13 @@ hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, i
 {
     if (capsules) hipLaunchKernelGGL(fr_capsule_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
     else hipLaunchKernelGGL(fr_obstacle_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_target_total(const DevCost *cost, const StepConst *steps, const double *rec, int H, bool compact,
+                                  const DevModel *model, double dt, double *out2, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_target_total_kernel, dim3(1), dim3(64), 0, s, cost, steps, rec, H, compact ? 1 : 0, model, dt, out2);
     return hipGetLastError();
 }
 

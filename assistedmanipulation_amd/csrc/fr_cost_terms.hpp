@@ -75,7 +75,8 @@ __device__ __forceinline__ double lagged_q(double q, double qd, double dt, bool 
 // World translations of bodies 2..9 (the sphere links PIVOT, PANDA_LINK1..7) at joint positions
 // qj[0..9]: fk_bodies' chain (fr_object.hip), pose_i = pose_parent o placement_i o joint_i, term for
 // term, with the rollout kernel's fsincos.  Bodies 0..9 are one chain (FR_PARENT[i] = i - 1).
-__device__ __forceinline__ void link_fk(const DevModel &M, const double *qj, double (*lp)[3])
+// R9 (or null): body 9's world rotation, row-major, which the chain carries to its end anyway
+__device__ __forceinline__ void link_fk(const DevModel &M, const double *qj, double (*lp)[3], double *R9 = nullptr)
 {
     const SinCosK K = sincos_constants();
     double R[9], p[3];
@@ -124,6 +125,10 @@ __device__ __forceinline__ void link_fk(const DevModel &M, const double *qj, dou
 #pragma unroll
             for (int k = 0; k < 3; k++) lp[i - (SC_LINK0 - 1)][k] = p[k];
         }
+    }
+    if (R9) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) R9[k] = R[k];
     }
 }
 
@@ -814,13 +819,101 @@ __device__ __forceinline__ void assisted_manipulation_terms(const DevCost &Cs, c
 // (in a rollout the record's own q_2)
 // LP: the self-collision term on the sphere links' positions lp (kinematic link-position model),
 // else the zero stub's constant
+// Target tracking (mppi_set_target_tracking): the step's target pose is tg (the StepConst seen as a
+// StepTarget) when the wave-uniform Cs.tp_track is on, else the descriptor's point.  The orientation
+// term w (3 - sum_ij Rt_ij Ree_ij) is added right behind the position term, before the joint,
+// self-collision and reach terms: Rt the rotation of the target's unit quaternion, Ree = R9 ee_R with
+// R9 body 9's world rotation at the lagged configuration of the link positions (link_fk).  A target
+// without an orientation (the zero quaternion) contributes 0.
+__device__ __forceinline__ double target_orientation_term(double w, double qx, double qy, double qz, double qw, const double *Ree)
+{
+    const double xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz;
+    const double xw = qx * qw, yw = qy * qw, zw = qz * qw;
+    const double Rt[9] = {1.0 - 2.0 * (yy + zz), 2.0 * (xy - zw),       2.0 * (xz + yw),
+                          2.0 * (xy + zw),       1.0 - 2.0 * (xx + zz), 2.0 * (yz - xw),
+                          2.0 * (xz - yw),       2.0 * (yz + xw),       1.0 - 2.0 * (xx + yy)};
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) s += Rt[k] * Ree[k];
+    const double n2 = (xx + yy) + (zz + qw * qw);
+    return (n2 == 0.0) ? 0.0 : w * (3.0 - s);
+}
+// Ree = R9 ee_R (row-major)
+__device__ __forceinline__ void grasp_rotation(const double *R9, const double *eeR, double *Ree)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) Ree[3 * r + c] = (R9[3 * r] * eeR[c] + R9[3 * r + 1] * eeR[3 + c]) + R9[3 * r + 2] * eeR[6 + c];
+    }
+}
+
+// The step's orientation term from body 9's rotation, formed where link_fk leaves R9 so that the
+// rotation is dead again before the other terms run (held across them, the obstacle units spilled)
+__device__ __forceinline__ double step_orientation_term(const DevCost &Cs, const StepTarget *tg, const double *R9, const DevModel &M)
+{
+    // row by row, each row's sum finished before the next begins: three entries of Rt and of Ree live
+    // at a time instead of eighteen beside the record and the link positions
+    const double qx = tg->q[0], qy = tg->q[1], qz = tg->q[2], qw = tg->qw;
+    const double xx = qx * qx, yy = qy * qy, zz = qz * qz;
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        double t0, t1, t2;
+        if (i == 0) { t0 = 1.0 - 2.0 * (yy + zz); t1 = 2.0 * (qx * qy - qz * qw); t2 = 2.0 * (qx * qz + qy * qw); }
+        else if (i == 1) { t0 = 2.0 * (qx * qy + qz * qw); t1 = 1.0 - 2.0 * (xx + zz); t2 = 2.0 * (qy * qz - qx * qw); }
+        else { t0 = 2.0 * (qx * qz - qy * qw); t1 = 2.0 * (qy * qz + qx * qw); t2 = 1.0 - 2.0 * (xx + yy); }
+        const double *R = R9 + 3 * i, *E = M.ee_R;
+        const double e0 = (R[0] * E[0] + R[1] * E[3]) + R[2] * E[6];
+        const double e1 = (R[0] * E[1] + R[1] * E[4]) + R[2] * E[7];
+        const double e2 = (R[0] * E[2] + R[1] * E[5]) + R[2] * E[8];
+        s += (t0 * e0 + t1 * e1) + t2 * e2;
+        asm volatile("" : "+v"(s));
+    }
+    const double n2 = (xx + yy) + (zz + qw * qw);
+    return (n2 == 0.0) ? 0.0 : Cs.tp_orient_w * (3.0 - s);
+}
+
+// The orientation term of a stored step record, as a function that is called, not inlined: it reads
+// the record's (q, qd) pairs again from memory and runs a pass of link_fk of its own, whose positions
+// nobody reads (the compiler drops them: the rotation chain alone).  Inlined into the objective - from
+// the terms' own link_fk pass or from a pass of its own - it cost every LP unit's TrackPoint kernels
+// 84 to 690 bytes of scratch per lane, spilled in the kernels' prologues whether the handle tracks or
+// not; called, its registers are saved and restored around the call, inside the wave-uniform branch
+// of a tracking handle, and the rollout units hold one copy of it each.
+static __device__ __attribute__((noinline)) double record_orientation_term(const double2 *src, const StepTarget *tg, const DevModel *M,
+                                                                  const DevCost *Cs, double dt, bool first)
+{
+    double qj[10], lpr[SC_LINKS][3], R9[9];
+#pragma unroll
+    for (int j = 0; j < 10; j++) {
+        const double2 v = src[j];
+        qj[j] = lagged_q(v.x, v.y, dt, first);
+    }
+    link_fk(*M, qj, lpr, R9);
+    return step_orientation_term(*Cs, tg, R9, *M);
+}
+
+// tg: a rollout's step (its target behind Cs.tp_track), orient its orientation term (behind
+// Cs.tp_track_orient); the device object's get_cost passes neither and reads the descriptor's point
 template <bool LP = false>
-__device__ __forceinline__ double track_point_cost(const DevCost &Cs, const double *r, double yaw, const double (*lp)[3] = nullptr)
+__device__ __forceinline__ double track_point_cost(const DevCost &Cs, const double *r, double yaw, const double (*lp)[3] = nullptr,
+                                                   const StepTarget *tg = nullptr, double orient = 0.0)
 {
     const double *ee = r + REC_EE, *am = r + REC_AM;
-    const double d0 = ee[0] - Cs.tp_point[0], d1 = ee[1] - Cs.tp_point[1], d2 = ee[2] - Cs.tp_point[2];
+    double g0 = Cs.tp_point[0], g1 = Cs.tp_point[1], g2 = Cs.tp_point[2];
+    const bool track = tg != nullptr && Cs.tp_track != 0;
+    if (track) {
+        g0 = tg->p[0];
+        g1 = tg->p[1];
+        g2 = tg->p[2];
+    }
+    const double d0 = ee[0] - g0, d1 = ee[1] - g1, d2 = ee[2] - g2;
     const double distance = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
     double cost = 100.0 * (distance * distance);   // point_cost: 100 pow(distance, 2)
+    if constexpr (LP) {
+        if (track && Cs.tp_track_orient) cost += orient;
+    }
     double joint = 0.0;
 #pragma unroll
     for (int j = 0; j < 10; j++) {
@@ -864,7 +957,11 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
                                            ObstacleRef ob = ObstacleRef{})
 {
     if constexpr (CK == CK_TRACK_POINT) {
+        // (a tracking handle's step constants hold the step's target: engine_types.hpp StepTarget)
+        const StepTarget *tg = reinterpret_cast<const StepTarget *>(&sc);
         if constexpr (LP) {
+            double orient = 0.0;
+            if (Cs.tp_track_orient) orient = record_orientation_term(src, tg, lm.model, &Cs, lm.dt, first);
             double lp[SC_LINKS][3];
             if (Cs.tp_en_self || OB) {
                 double qj[10];
@@ -873,11 +970,12 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
                 link_fk(*lm.model, qj, lp);
             }
             if constexpr (OB)
-                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp) + obstacle_cost<OB>(ob, lp, r + REC_EE, lm.dt));
+                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp, tg, orient) +
+                                     obstacle_cost<OB>(ob, lp, r + REC_EE, lm.dt));
             else
-                return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp);
+                return sc.gamma_k * track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp, tg, orient);
         } else {
-            return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4]);
+            return sc.gamma_k * track_point_cost(Cs, r, r[REC_QQD + 4], nullptr, tg);
         }
     } else {
         if constexpr (OB) return sc.gamma_k * assisted_manipulation_cost<EN, JS, KC, JG, true, OB>(Cs, sc, r, Lj, src, lm, first, ob);

@@ -467,7 +467,25 @@ __global__ __launch_bounds__(64) void fr_object_field_kernel(const DevPinocchio 
     *out1 = mppi_cost::field_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION);
 }
 
+// mppi_dynamics_target_cost: the target-tracking terms (fr_cost_terms.hpp track_point_cost) at the
+// grasp frame's cached pose - its position and its rotation R9 ee_R as the last calculate() left them
+__global__ __launch_bounds__(64) void fr_object_target_kernel(const DevPinocchio *obj, ObjTarget t, double *out2)
+{
+    if (threadIdx.x != 0) return;
+    const double *ee = obj->ee + MPPI_EE_POSITION;
+    const double d0 = ee[0] - t.point[0], d1 = ee[1] - t.point[1], d2 = ee[2] - t.point[2];
+    const double distance = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+    out2[0] = 100.0 * (distance * distance);
+    out2[1] = t.has_q ? mppi_cost::target_orientation_term(t.w, t.q[0], t.q[1], t.q[2], t.q[3], obj->ee + MPPI_EE_ROTATION) : 0.0;
+}
+
 namespace mppi_eng {
+
+hipError_t launch_fr_object_target(const DevPinocchio *obj, const ObjTarget &t, double *out2, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_object_target_kernel, dim3(1), dim3(64), 0, s, obj, t, out2);
+    return hipGetLastError();
+}
 
 hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
 {

@@ -532,5 +532,33 @@ hipError_t launch_fr_field_total(const StepConst *steps, const double *rec, int 
                                  double dt, double *out1, hipStream_t s);
 hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
 
+// Target tracking (mppi_set_target_tracking, mppi_set_target_path): the timed pose path as the host
+// stored it - quaternions normalised and sign-fixed, inv[i] = 1 / (time[i + 1] - time[i]) - and the
+// update's t0 and dt, all by value.  launch_target_table samples it at t0 + k dt for k < H into the
+// target fields of out[k] (engine_types.hpp StepTarget; gamma_k is left alone): the ends are held,
+// position and quaternion are interpolated linearly, the quaternion renormalised.  n = 0: `point`
+// in every step and no orientation; has_q = 0: positions only (the zero quaternion).
+struct TargetPathArgs {
+    int n, has_q, H, pad;
+    double t0, dt;
+    double point[3];
+    double time[TARGET_WAYPOINTS_MAX], inv[TARGET_WAYPOINTS_MAX];
+    double p[TARGET_WAYPOINTS_MAX][3], q[TARGET_WAYPOINTS_MAX][4];
+    StepConst *out;
+};
+hipError_t launch_target_table(const TargetPathArgs &a, hipStream_t s);
+// The position and orientation terms of one rollout's H records, each summed over its steps in step
+// order, undiscounted (mppi_optimal_target_cost), with the targets in `steps`; model: the kinematic
+// link-position model's (null: no orientation term, out2[1] = 0)
+hipError_t launch_fr_target_total(const DevCost *cost, const StepConst *steps, const double *rec, int H, bool compact,
+                                  const DevModel *model, double dt, double *out2, hipStream_t s);
+// mppi_dynamics_target_cost: 100 |p_EE - point|^2 and, with has_q, w (3 - sum_ij Rt_ij Ree_ij) at the
+// object's cached grasp-frame pose; q is a unit quaternion (x, y, z, w)
+struct ObjTarget {
+    double point[3], q[4], w;
+    int has_q, pad;
+};
+hipError_t launch_fr_object_target(const DevPinocchio *obj, const ObjTarget &t, double *out2, hipStream_t s);
+
 
 }  // namespace mppi_eng

@@ -222,6 +222,19 @@ class PinocchioDynamicsObject:
         self._check(self._L.mppi_dynamics_obstacle_cost(self._h, C.byref(c), arr, n, float(elapsed), C.byref(v)))
         return v.value
 
+    def target_cost(self, point, quaternion=None, config=None):
+        """mppi_dynamics_target_cost: the target-tracking terms (Trajectory.set_target_tracking) at the
+        grasp frame's pose the object cached at its last call: (100 |p_EE - point|^2, weight (3 -
+        sum_ij Rt_ij Ree_ij)), the second 0 without a `quaternion` (x, y, z, w; normalised by the
+        engine).  `config`: a TargetTracking or None (the defaults)."""
+        from .targets import TargetTracking
+        c = (config or TargetTracking()).to_c()
+        p = np.ascontiguousarray(point, dtype=np.float64).reshape(3)
+        q = None if quaternion is None else np.ascontiguousarray(quaternion, dtype=np.float64).reshape(4)
+        o = np.zeros(2)
+        self._check(self._L.mppi_dynamics_target_cost(self._h, _p(p), None if q is None else _p(q), C.byref(c), _p(o)))
+        return float(o[0]), float(o[1])
+
     def query_row(self):
         """The members after the last call as MPPI_DYNAMICS_QUERY_N doubles."""
         o = np.zeros(abi.MPPI_DYNAMICS_QUERY_N)

@@ -19,6 +19,7 @@ import numpy as np
 from . import abi
 from ._lib import load
 from .obstacles import ObstacleAvoidance, ObstacleCapsules, obstacle_from_c, obstacles_to_c
+from .targets import TargetPath, TargetTracking
 from .config import Configuration
 from .safety import TrajectorySafetyFilter
 
@@ -447,6 +448,45 @@ class Trajectory:
         v = C.c_double(0.0)
         self._check(self._L.mppi_optimal_obstacle_cost(self._h, C.byref(v)))
         return v.value
+
+    def set_target_tracking(self, config=None):
+        """mppi_set_target_tracking: TrackPoint follows a timed pose path (set_target_path) instead of
+        its fixed point, with `config` (a TargetTracking; None: the defaults, position only).
+        FrankaRidgeback handles with the TrackPoint objective, before the first update; orientation
+        tracking needs the kinematic link-position model.  It cannot be undone."""
+        c = (config or TargetTracking()).to_c()
+        self._check(self._L.mppi_set_target_tracking(self._h, C.byref(c)))
+
+    @property
+    def target_tracking(self):
+        """The TargetTracking in force, or None when tracking is off (mppi_get_target_tracking)."""
+        on, c = C.c_int(0), abi.mppi_target_tracking_config()
+        self._check(self._L.mppi_get_target_tracking(self._h, C.byref(on), C.byref(c)))
+        return TargetTracking.from_c(c) if on.value else None
+
+    def set_target_path(self, path):
+        """mppi_set_target_path: replace the path (a TargetPath, or a raw abi.mppi_target_path; None
+        clears it, and the target is the objective's point again).  Between any two updates; every
+        rank of a sharded run sets the same one."""
+        if path is None:
+            self._check(self._L.mppi_set_target_path(self._h, None))
+            return
+        c = path if isinstance(path, abi.mppi_target_path) else path.to_c()
+        self._check(self._L.mppi_set_target_path(self._h, C.byref(c)))
+
+    def target_path(self):
+        """The current path as the engine stored it (quaternions normalised and sign-fixed), or None
+        (mppi_get_target_path)."""
+        c, present = abi.mppi_target_path(), C.c_int(0)
+        self._check(self._L.mppi_get_target_path(self._h, C.byref(c), C.byref(present)))
+        return TargetPath.from_c(c) if present.value else None
+
+    def get_optimal_target_cost(self):
+        """mppi_optimal_target_cost: (position total, orientation total) of the last update's filter()
+        row over its steps, undiscounted."""
+        o = np.zeros(2)
+        self._check(self._L.mppi_optimal_target_cost(self._h, _p(o)))
+        return float(o[0]), float(o[1])
 
     def set_noise_source(self, source, seed=0x5EED):
         self._check(self._L.mppi_set_noise_source(self._h, int(source), int(seed)))

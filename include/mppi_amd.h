@@ -566,6 +566,64 @@ mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *f
 mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, int *present);
 mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost);
 
+/* Target tracking: TrackPoint follows a timed end-effector pose path over the horizon instead of
+ * one fixed point.  The reference describes such targets (controller/trajectory.hpp) but feeds none
+ * to an objective; here they are an opt-in mode of TrackPoint.  Nothing changes unless it is enabled.
+ *
+ * mppi_set_target_tracking (config NULL: mppi_default_target_tracking_config, {10.0, 0}) selects the
+ * mode for the handle's life: FrankaRidgeback handles with MPPI_COST_TRACK_POINT only
+ * (MPPI_ERR_UNSUPPORTED otherwise), before the first update (MPPI_ERR_INVALID after it), and not
+ * together with an attached forecast (mppi_forecast_attach, whose step constants share the fields the
+ * targets live in: MPPI_ERR_INVALID either way round).  orientation_weight must be finite and >= 0.
+ * track_orientation = 1 needs MPPI_LINK_POSITIONS_KINEMATIC (MPPI_ERR_INVALID otherwise, the message
+ * says which condition failed), and the link-position model is fixed from then on; position tracking
+ * works in every link mode.  mppi_get_target_tracking: enabled = 0 for a handle that never enabled
+ * it (out untouched).
+ *
+ * A path (mppi_set_target_path, between any two updates; NULL clears it) is 1 <= count <=
+ * MPPI_TARGET_WAYPOINTS_MAX waypoints: finite, strictly increasing times, finite positions and, with
+ * has_orientation, finite quaternions (x, y, z, w, MPPI_EE_QUATERNION's order) of norm in [0.5, 2].
+ * On set each quaternion is normalised in fp64, then waypoint i + 1's is negated whenever its dot
+ * product with waypoint i's (already fixed) is negative; mppi_get_target_path returns the path as
+ * stored (present = 0: none).  Anything invalid is MPPI_ERR_INVALID with a message, and the path
+ * that was set before stays.  The sample at time t: waypoint 0 for t <= time[0], waypoint count - 1
+ * for t >= time[count - 1]; otherwise, with i the greatest index with time[i] <= t and
+ * f = (t - time[i]) * (1 / (time[i + 1] - time[i])), p = p_i + f (p_{i+1} - p_i) and
+ * q = q_i + f (q_{i+1} - q_i) divided by its norm (>= sqrt(1/2) after the sign fix).
+ *
+ * The cost of step k of an update at t0 on a tracking handle, t_k = t0 + k dt (the time get_cost is
+ * called with): the position term 100 pow(|p_EE - p(t_k)|, 2) (without a path p is the descriptor's
+ * point), p_EE the grasp-frame position track_point_cost reads; then, with track_orientation and a
+ * path that has orientations, orientation_weight * (3 - sum_ij Rt_ij Ree_ij) = 4 w sin^2(theta / 2),
+ * Rt the rotation matrix of q(t_k), Ree = R_9 ee_R with R_9 body 9's world rotation at the lagged
+ * configuration the link positions use (q_0 for step 0, else q - qd dt); then the joint-limit,
+ * self-collision and reach terms, and the sum is discounted; the obstacle term follows as before.
+ * The update that ran keeps its own targets for its filter() row.
+ * mppi_optimal_target_cost: out2 = the position and the orientation totals of the last update's
+ * filter() row, undiscounted (zeros before the first published update; MPPI_ERR_UNSUPPORTED when
+ * tracking is off).  Added like the obstacle symbols, without a version change: detect by symbol. */
+#define MPPI_TARGET_WAYPOINTS_MAX 32
+typedef struct mppi_target_tracking_config {
+    double orientation_weight;
+    int32_t track_orientation;
+} mppi_target_tracking_config;
+typedef struct mppi_target_waypoint {
+    double time;
+    double position[3];
+    double quaternion[4];
+} mppi_target_waypoint;
+typedef struct mppi_target_path {
+    int32_t count;
+    int32_t has_orientation;
+    mppi_target_waypoint waypoints[MPPI_TARGET_WAYPOINTS_MAX];
+} mppi_target_path;
+void mppi_default_target_tracking_config(mppi_target_tracking_config *out);
+mppi_status mppi_set_target_tracking(mppi_handle *h, const mppi_target_tracking_config *config);
+mppi_status mppi_get_target_tracking(mppi_handle *h, int *enabled, mppi_target_tracking_config *out);
+mppi_status mppi_set_target_path(mppi_handle *h, const mppi_target_path *path);
+mppi_status mppi_get_target_path(mppi_handle *h, mppi_target_path *out, int *present);
+mppi_status mppi_optimal_target_cost(mppi_handle *h, double *out2);
+
 /* The trajectory safety filter: FrankaRidgeback::TrajectorySafetyFilter::Configuration
  * (frankaridgeback/safety.hpp:15-40) field for field.  The reference declares the class and leaves
  * its methods empty; here the configuration is live, opt-in (no filter unless one is set).  The
@@ -844,6 +902,13 @@ mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_con
 mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
                                               const mppi_capsule_config *capsules, const mppi_distance_field *field,
                                               const float *values, double *cost);
+/* The target-tracking terms (mppi_set_target_tracking above) at the object's cached grasp-frame pose
+ * after its last call: out2[0] = 100 pow(|p_EE - point|, 2), out2[1] = orientation_weight *
+ * (3 - sum_ij Rt_ij Ree_ij) for `quaternion` (x, y, z, w; finite, norm in [0.5, 2], normalised here)
+ * or 0 with quaternion NULL.  config NULL: the defaults; its track_orientation is not read.  Works
+ * in either link-position mode: the object caches the frame's rotation in both. */
+mppi_status mppi_dynamics_target_cost(mppi_dynamics *d, const double *point3, const double *quaternion4,
+                                      const mppi_target_tracking_config *config, double *out2);
 /* add_end_effector_simulated_wrench (6 doubles: force, moment; semantics above): cumulative; the
  * next mppi_dynamics_step applies the sum and zeroes it.  get_end_effector_simulated_wrench: the
  * wrench the last step applied, zeros before any step. */

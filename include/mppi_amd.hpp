@@ -363,6 +363,35 @@ public:
         if (mppi_optimal_obstacle_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
         return c;
     }
+    // Target tracking (mppi_set_target_tracking; nullptr: the defaults, position only): TrackPoint
+    // follows a timed pose path.  A FrankaRidgeback trajectory with the TrackPoint objective, before
+    // the first update; false and a message on stderr otherwise.
+    bool set_target_tracking(const mppi_target_tracking_config *config = nullptr)
+    {
+        if (mppi_set_target_tracking(m_h, config) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // whether it is on, and the configuration it runs with
+    bool target_tracking(mppi_target_tracking_config *out = nullptr) const
+    {
+        int on = 0;
+        return mppi_get_target_tracking(m_h, &on, out) == MPPI_OK && on != 0;
+    }
+    // the path (mppi_set_target_path; nullptr: none, the objective's point again): between any two updates
+    bool set_target_path(const mppi_target_path *path)
+    {
+        if (mppi_set_target_path(m_h, path) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    // the position and orientation terms of the optimal rollout, each summed over its steps (mppi_optimal_target_cost)
+    std::array<double, 2> get_optimal_target_cost()
+    {
+        std::array<double, 2> c = {0.0, 0.0};
+        if (mppi_optimal_target_cost(m_h, c.data()) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
+        return c;
+    }
     Trajectory(const Trajectory &) = delete;
     Trajectory &operator=(const Trajectory &) = delete;
 
@@ -677,6 +706,15 @@ public:
     {
         double c = 0.0;
         check(mppi_dynamics_distance_field_cost(object(), config, capsules, &field, values, &c));
+        return c;
+    }
+    // the target-tracking terms at the grasp frame's cached pose (mppi_dynamics_target_cost): position,
+    // orientation (0 with quaternion nullptr; x, y, z, w)
+    std::array<double, 2> target_cost(const double *point3, const double *quaternion4 = nullptr,
+                                      const mppi_target_tracking_config *config = nullptr)
+    {
+        std::array<double, 2> c = {0.0, 0.0};
+        check(mppi_dynamics_target_cost(object(), point3, quaternion4, config, c.data()));
         return c;
     }
     std::vector<double> get_joint_position() { return query(0, 12); }
