@@ -131,6 +131,16 @@ PROTOTYPES = {
     "mppi_dynamics_target_cost": (C.c_int, [_h, _dp, _dp, C.POINTER(abi.mppi_target_tracking_config), _dp]),
     "mppi_dynamics_distance_field_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_capsule_config),
                                                     C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float), _dp]),
+    "mppi_set_held_object_avoidance": (C.c_int, [_h]),
+    "mppi_get_held_object_avoidance": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_set_held_object": (C.c_int, [_h, C.POINTER(abi.mppi_held_object)]),
+    "mppi_get_held_object": (C.c_int, [_h, C.POINTER(abi.mppi_held_object), C.POINTER(C.c_int)]),
+    "mppi_optimal_held_cost": (C.c_int, [_h, _dp]),
+    "mppi_predicted_held_optimal": (C.c_int, [_h, _dp]),
+    "mppi_predicted_held_rollouts": (C.c_int, [_h, _i64p, C.c_int64, _dp]),
+    "mppi_dynamics_held_object_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_obstacle), C.c_int32,
+                                                 C.c_double, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float),
+                                                 C.POINTER(abi.mppi_held_object), _dp]),
 }
 
 _lib = None

@@ -208,6 +208,25 @@ class mppi_distance_field(C.Structure):
                 ("origin", _d * 3), ("voxel", C.c_double)]
 
 
+# mppi_set_held_object
+MPPI_HELD_POINTS = 4
+MPPI_HELD_SEGMENTS = 3
+MPPI_OBSTACLE_MASK_HELD = 0x07001E00
+
+
+def MPPI_OBSTACLE_MASK_HELD_POINT(i):
+    return 1 << (9 + i)
+
+
+def MPPI_OBSTACLE_MASK_HELD_SEGMENT(s):
+    return 1 << (24 + s)
+
+
+class mppi_held_object(C.Structure):
+    _fields_ = [("count", C.c_int32), ("pad", C.c_int32), ("centres", (_d * 3) * MPPI_HELD_POINTS), ("radii", _d * MPPI_HELD_POINTS),
+                ("segment_radii", _d * MPPI_HELD_SEGMENTS)]
+
+
 class mppi_safety_filter_desc(C.Structure):
     """TrajectorySafetyFilter::Configuration (frankaridgeback/safety.hpp:15-40) -> include/mppi_amd.h."""
     _fields_ = [

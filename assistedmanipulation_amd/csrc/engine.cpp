@@ -126,7 +126,7 @@ bool check_capsule_config(const mppi_capsule_config &c, std::string &why)
 }
 
 // mppi_set_distance_field's / mppi_dynamics_distance_field_cost's descriptor and values
-bool check_distance_field(const mppi_distance_field &f, const float *values, std::string &why)
+bool check_distance_field(const mppi_distance_field &f, const float *values, std::string &why, bool held = false)
 {
     int64_t n = 1;
     for (int a = 0; a < 3; a++) {
@@ -149,8 +149,12 @@ bool check_distance_field(const mppi_distance_field &f, const float *values, std
         why = "distance field: voxel must be finite and > 0";
         return false;
     }
-    if (f.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS)) {
+    if (!held && (f.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS))) {
         why = "distance field: mask has bits outside the points (0..8) and the segments (16..23)";
+        return false;
+    }
+    if (held && (f.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS | MPPI_OBSTACLE_MASK_HELD))) {
+        why = "distance field: mask has bits outside the points (0..8), the segments (16..23) and the held object (9..12, 24..26)";
         return false;
     }
     if (f.segment_samples < 0 || f.segment_samples > MPPI_DISTANCE_FIELD_MAX_SAMPLES) {
@@ -185,9 +189,62 @@ void fill_field(DevField &d, const mppi_distance_field &f, const float *grid)
         d.phi[j] = j < f.segment_samples ? (double)(j + 1) / (double)(f.segment_samples + 1) : 0.0;
 }
 
+// mppi_set_held_object's / mppi_dynamics_held_object_cost's object: the values of the points and
+// segments it has
+bool check_held_object(const mppi_held_object &o, std::string &why)
+{
+    if (o.count < 0 || o.count > MPPI_HELD_POINTS) {
+        why = "held object: count must be in [0, 4]";
+        return false;
+    }
+    for (int i = 0; i < o.count; i++) {
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(o.centres[i][a])) {
+                why = "held object: centres[" + std::to_string(i) + "] must be finite";
+                return false;
+            }
+        if (!std::isfinite(o.radii[i]) || o.radii[i] < 0.0) {
+            why = "held object: radii[" + std::to_string(i) + "] must be finite and >= 0";
+            return false;
+        }
+    }
+    for (int s = 0; s + 1 < o.count; s++)
+        if (!std::isfinite(o.segment_radii[s]) || o.segment_radii[s] < 0.0) {
+            why = "held object: segment_radii[" + std::to_string(s) + "] must be finite and >= 0";
+            return false;
+        }
+    return true;
+}
+
+// The table's third tail of a checked object: the points and segments it has, zeros behind them
+void fill_held(DevHeld &d, const mppi_held_object &o)
+{
+    d = DevHeld{};
+    d.count = o.count;
+    for (int i = 0; i < o.count; i++) {
+        for (int a = 0; a < 3; a++) d.centres[i][a] = o.centres[i][a];
+        d.radii[i] = o.radii[i];
+    }
+    for (int s = 0; s + 1 < o.count; s++) d.seg_radii[s] = o.segment_radii[s];
+}
+
+// The object as the handle keeps it: what it does not have is zero
+mppi_held_object canonical_held(const mppi_held_object &o)
+{
+    mppi_held_object c{};
+    c.count = o.count;
+    for (int i = 0; i < o.count; i++) {
+        for (int a = 0; a < 3; a++) c.centres[i][a] = o.centres[i][a];
+        c.radii[i] = o.radii[i];
+    }
+    for (int s = 0; s + 1 < o.count; s++) c.segment_radii[s] = o.segment_radii[s];
+    return c;
+}
+
 // mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set (capsules: a capsule handle's, or
-// mppi_dynamics_capsule_cost's - the capsule kind and the segment bits of a mask are legal)
-bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why, bool capsules = false)
+// mppi_dynamics_capsule_cost's - the capsule kind and the segment bits of a mask are legal; held: a
+// held handle's, or mppi_dynamics_held_object_cost's - the held bits are legal too)
+bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::string &why, bool capsules = false, bool held = false)
 {
     if (count < 0 || count > MPPI_MAX_OBSTACLES) {
         why = "obstacles: count must be in [0, " + std::to_string(MPPI_MAX_OBSTACLES) + "]";
@@ -216,8 +273,12 @@ bool check_obstacles(const mppi_obstacle *set, int32_t count, double time, std::
             why = at + "mask has bits above bit 8";
             return false;
         }
-        if (capsules && (b.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS))) {
+        if (capsules && !held && (b.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS))) {
             why = at + "mask has bits outside the points (0..8) and the segments (16..23)";
+            return false;
+        }
+        if (capsules && held && (b.mask & ~(MPPI_OBSTACLE_MASK_ALL | MPPI_OBSTACLE_MASK_SEGMENTS | MPPI_OBSTACLE_MASK_HELD))) {
+            why = at + "mask has bits outside the points (0..8), the segments (16..23) and the held object (9..12, 24..26)";
             return false;
         }
         bool finite = std::isfinite(b.radius);
@@ -398,6 +459,11 @@ struct mppi_handle {
     float *h_field_stage = nullptr;
     size_t field_stage_cap = 0;
     hipEvent_t ev_field = nullptr;
+    // mppi_set_held_object_avoidance: the held-object kernels (FR_LINKS_HELD), fixed once enabled.
+    // mppi_set_held_object: the object the next update's table carries (held_present false: nothing is
+    // held); held_update: the object the last update ran with (mppi_predicted_held_*'s absent rows)
+    bool held_avoidance = false, held_present = false;
+    mppi_held_object held{}, held_update{};
     // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
     // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
     // (phase3_launch).  safety_ran: the last phase 3 ran it (d_out_stage holds that update's
@@ -1315,6 +1381,44 @@ mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obsta
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
+                                           int32_t count, double elapsed, const mppi_distance_field *field, const float *values,
+                                           const mppi_held_object *object, double *cost)
+{
+    if (!d || !cost) return MPPI_ERR_INVALID;
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    std::string why;
+    if (!check_obstacle_config(c, why) || !check_obstacles(obstacles, count, elapsed, why, true, true)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (field && !check_distance_field(*field, values, why, true)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (object && !check_held_object(*object, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (!object || object->count == 0) {   // nothing held: no term
+        *cost = 0.0;
+        return MPPI_OK;
+    }
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    DHIP_TRY(hipSetDevice(d->device));
+    ObstacleTable t{};
+    fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0);
+    fill_held(t.held, *object);
+    float *grid = nullptr;
+    hipError_t e = hipSuccess;
+    if (field) {
+        const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
+        DHIP_TRY(hipMalloc((void **)&grid, n * sizeof(float)));
+        fill_field(t.field, *field, grid);
+        e = hipMemcpyAsync(grid, values, n * sizeof(float), hipMemcpyHostToDevice, d->stream);
+    }
+    if (e == hipSuccess) e = launch_fr_object_held(d->d_obj, t, d->d_buf, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (grid) (void)hipFree(grid);
+    DHIP_TRY(e);
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
                                         double *out12)
 {
@@ -2070,6 +2174,7 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
 // FrRolloutArgs::link_positions of the handle's launches
 static int launch_link_mode(const mppi_handle *h)
 {
+    if (h->obstacle_avoidance && h->held_avoidance) return FR_LINKS_HELD;
     if (h->obstacle_avoidance && h->field_avoidance) return FR_LINKS_FIELD;
     if (h->obstacle_avoidance) return h->obstacle_capsules ? FR_LINKS_CAPSULES : FR_LINKS_OBSTACLES;
     return h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? FR_LINKS_KINEMATIC : FR_LINKS_ZERO;
@@ -2176,6 +2281,10 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
     if (h->field_avoidance) {   // the current field's grid: the next set leaves it alone
         if (h->field_present) fill_field(t.field, h->field, h->d_field[h->field_cur]);
         h->field_last = h->field_present ? h->field_cur : -1;
+    }
+    if (h->held_avoidance) {   // the object as it stands: this update's, whatever is set later
+        h->held_update = h->held_present ? h->held : mppi_held_object{};
+        fill_held(t.held, h->held_update);
     }
     HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
     return MPPI_OK;
@@ -3089,7 +3198,7 @@ mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, i
     if (!h) return MPPI_ERR_INVALID;
     if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
     std::string why;
-    if (!check_obstacles(obstacles, count, time, why, h->obstacle_capsules)) return fail(h, MPPI_ERR_INVALID, why);
+    if (!check_obstacles(obstacles, count, time, why, h->obstacle_capsules, h->held_avoidance)) return fail(h, MPPI_ERR_INVALID, why);
     for (int32_t o = 0; o < count; o++) h->ob_set[o] = obstacles[o];
     h->ob_count = count;
     h->ob_time = time;
@@ -3166,7 +3275,7 @@ mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *f
         return MPPI_OK;
     }
     std::string why;
-    if (!check_distance_field(*field, values, why)) return fail(h, MPPI_ERR_INVALID, why);
+    if (!check_distance_field(*field, values, why, h->held_avoidance)) return fail(h, MPPI_ERR_INVALID, why);
     HIP_TRY(hipSetDevice(h->device));
     const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
     // the grid the last update's table does not reference: that update's filter() row may not have run
@@ -3207,6 +3316,51 @@ mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, in
         return fail(h, MPPI_ERR_INVALID, "distance field: field avoidance is not enabled (mppi_set_distance_field_avoidance)");
     *present = h->field_present ? 1 : 0;
     if (h->field_present && out) *out = h->field;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_held_object_avoidance(mppi_handle *h)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->field_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held object avoidance: distance field avoidance is not enabled (mppi_set_distance_field_avoidance)");
+    // the held-object kernels are part of the launch plan and of a captured graph, like the field kernels
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "held object avoidance is enabled before the first update");
+    h->held_avoidance = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_held_object_avoidance(mppi_handle *h, int *enabled)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->held_avoidance ? 1 : 0;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_held_object(mppi_handle *h, const mppi_held_object *object)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->held_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held object: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
+    if (!object) {   // put down: nothing is held from the next update on
+        h->held_present = false;
+        return MPPI_OK;
+    }
+    std::string why;
+    if (!check_held_object(*object, why)) return fail(h, MPPI_ERR_INVALID, why);
+    // (host state only: the next update's table carries it, so a pending filter() row keeps its own)
+    h->held = canonical_held(*object);
+    h->held_present = object->count > 0;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_held_object(mppi_handle *h, mppi_held_object *out, int *present)
+{
+    if (!h || !present) return MPPI_ERR_INVALID;
+    if (!h->held_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held object: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
+    *present = h->held_present ? 1 : 0;
+    if (h->held_present && out) *out = h->held;
     return MPPI_OK;
 }
 
@@ -3504,9 +3658,14 @@ mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
     if (h->field_avoidance)   // a field handle: the capsule term plus the field term
         HIP_TRY(launch_fr_field_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 1,
                                       h->stream_opt));
-    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, (h->field_avoidance ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    if (h->held_avoidance)   // a held handle: (capsule + field) + held
+        HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 2,
+                                     h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, (h->held_avoidance ? 3 : (h->field_avoidance ? 2 : 1)) * sizeof(double),
+                           hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->field_avoidance ? h->h_opt[1] + h->h_opt[2] : h->h_opt[1];
+    if (h->held_avoidance) *cost += h->h_opt[3];
     return MPPI_OK;
 }
 
@@ -3649,12 +3808,32 @@ mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost)
     return MPPI_OK;
 }
 
+mppi_status mppi_optimal_held_cost(mppi_handle *h, double *cost)
+{
+    if (!h || !cost) return MPPI_ERR_INVALID;
+    if (!h->held_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "held cost: held object avoidance is not enabled");
+    HIP_TRY(hipSetDevice(h->device));
+    *cost = 0.0;
+    if (!h->published_once) return MPPI_OK;   // no filter() row yet
+    mppi_status st = wait_optimal(h);
+    if (st != MPPI_OK) return st;
+    // (the row's own update's table, and through it that update's object and grid)
+    HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
+                                 h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    HIP_TRY(hipStreamSynchronize(h->stream_opt));
+    *cost = h->h_opt[1];
+    return MPPI_OK;
+}
+
 // Predicted trajectories (fr_predict.hip): `rows` (host) address n rollouts' records in `rec`; the
 // kernel runs on `s`, one device-to-host copy follows, then a synchronise.  The buffers grow with
 // the request and stay with the handle.
-static mppi_status predicted_run(mppi_handle *h, const double *rec, const std::vector<PredictRow> &rows, hipStream_t s, double *out)
+// held (or null): the held points' paths instead (fr_predict_held_kernel), MPPI_HELD_POINTS x 3 doubles a step
+static mppi_status predicted_run(mppi_handle *h, const double *rec, const std::vector<PredictRow> &rows, hipStream_t s, double *out,
+                                 const DevHeld *held = nullptr)
 {
-    const size_t n = rows.size(), doubles = n * (size_t)h->H * MPPI_PRED_N;
+    const size_t n = rows.size(), doubles = n * (size_t)h->H * (held ? (size_t)MPPI_HELD_POINTS * 3 : (size_t)MPPI_PRED_N);
     if (n > h->pred_rows_cap) {
         dfree(h, h->d_pred_rows);
         h->pred_rows_cap = 0;
@@ -3670,30 +3849,52 @@ static mppi_status predicted_run(mppi_handle *h, const double *rec, const std::v
     const bool energy = h->cost_kind == MPPI_COST_ASSISTED_MANIPULATION && h->am.enable_energy_limit;   // phase 1's a.energy
     // (the caller's `rows` outlive the synchronise below)
     HIP_TRY(hipMemcpyAsync(h->d_pred_rows, rows.data(), n * sizeof(PredictRow), hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_fr_predict(h->d_model, rec, h->d_pred_rows, (int64_t)n, (int)h->H, energy ? 1 : 0, h->d_pred_out, s));
+    if (held) HIP_TRY(launch_fr_predict_held(h->d_model, rec, h->d_pred_rows, (int64_t)n, (int)h->H, *held, h->d_pred_out, s));
+    else HIP_TRY(launch_fr_predict(h->d_model, rec, h->d_pred_rows, (int64_t)n, (int)h->H, energy ? 1 : 0, h->d_pred_out, s));
     HIP_TRY(hipMemcpyAsync(out, h->d_pred_out, doubles * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return MPPI_OK;
 }
 
-mppi_status mppi_predicted_optimal(mppi_handle *h, double *out)
+// held: mppi_predicted_held_optimal (the held points of the last update's object)
+static mppi_status predicted_optimal(mppi_handle *h, double *out, bool held)
 {
     if (!h || !out) return MPPI_ERR_INVALID;
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
+    if (held && !h->held_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "predicted held paths: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     if (!h->published_once) return fail(h, MPPI_ERR_INVALID, "predicted optimal rollout: no update has published yet");
     HIP_TRY(hipSetDevice(h->device));
     mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
     if (st != MPPI_OK) return st;
     const std::vector<PredictRow> rows{PredictRow{0, h->opt_rec_compact ? 1 : 0, 0}};
-    return predicted_run(h, h->d_rec_opt, rows, h->stream_opt, out);
+    if (!held) return predicted_run(h, h->d_rec_opt, rows, h->stream_opt, out);
+    DevHeld dh;
+    fill_held(dh, h->held_update);
+    return predicted_run(h, h->d_rec_opt, rows, h->stream_opt, out, &dh);
 }
 
+mppi_status mppi_predicted_optimal(mppi_handle *h, double *out) { return predicted_optimal(h, out, false); }
+mppi_status mppi_predicted_held_optimal(mppi_handle *h, double *out) { return predicted_optimal(h, out, true); }
+
+static mppi_status predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out, bool held);
 mppi_status mppi_predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out)
+{
+    return predicted_rollouts(h, rollouts, n, out, false);
+}
+mppi_status mppi_predicted_held_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out)
+{
+    return predicted_rollouts(h, rollouts, n, out, true);
+}
+
+static mppi_status predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out, bool held)
 {
     if (!h || n < 0 || (n > 0 && (!rollouts || !out))) return MPPI_ERR_INVALID;
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
+    if (held && !h->held_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "predicted held paths: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     if (!h->updated_once) return fail(h, MPPI_ERR_INVALID, "predicted rollouts: no update has run yet");
     if (h->info[MPPI_INFO_WAIT_TIMEOUTS] != 0)
         return fail(h, MPPI_ERR_DEVICE, "predicted rollouts: the last update's launch lost rows (in-launch wait timeouts)");
@@ -3711,7 +3912,10 @@ mppi_status mppi_predicted_rollouts(mppi_handle *h, const int64_t *rollouts, int
     }
     if (n == 0) return MPPI_OK;
     HIP_TRY(hipSetDevice(h->device));
-    return predicted_run(h, h->d_rec, rows, h->stream, out);
+    if (!held) return predicted_run(h, h->d_rec, rows, h->stream, out);
+    DevHeld dh;
+    fill_held(dh, h->held_update);
+    return predicted_run(h, h->d_rec, rows, h->stream, out, &dh);
 }
 
 mppi_status mppi_argmin(mppi_handle *h, int64_t *rollout)

@@ -136,6 +136,18 @@ struct DevField {
     int samples, pad;
     double phi[OB_FIELD_SAMPLES];
 };
+// ... and, behind those, a held object (mppi_set_held_object_avoidance)
+constexpr int OB_TERM_HELD = 4;
+// The held object of one update: `count` spheres fixed in the grasp frame (centres in metres, radii)
+// and the segments between consecutive ones; count 0: nothing is held.  Held point i is mask bit
+// OB_HELD_POINT_BIT0 + i, held segment s bit OB_HELD_SEGMENT_BIT0 + s, in the obstacles' masks and the field's.
+constexpr int OB_HELD_POINTS = 4, OB_HELD_SEGMENTS = 3, OB_HELD_POINT_BIT0 = 9, OB_HELD_SEGMENT_BIT0 = 24;
+struct DevHeld {
+    int count, pad;
+    double centres[OB_HELD_POINTS][3];
+    double radii[OB_HELD_POINTS];
+    double seg_radii[OB_HELD_SEGMENTS];
+};
 struct DevObstacle {
     double position[3], velocity[3], normal[3], radius;
     int kind;
@@ -149,6 +161,7 @@ struct ObstacleTable {
     DevObstacle ob[OB_MAX];
     double seg_radii[OB_SEGMENTS];   // capsule handles only (zeros otherwise)
     DevField field;                  // field handles only (zeros otherwise): behind everything the other kernels read
+    DevHeld held;                    // held handles only (zeros otherwise): behind the field, so every older offset stays
 };
 // the table's room behind the 2 H step-constant slots, in StepConst units
 constexpr int OB_TABLE_STEPS = (int)((sizeof(ObstacleTable) + sizeof(StepConst) - 1) / sizeof(StepConst));

@@ -490,6 +490,188 @@ __device__ __forceinline__ double field_term(TP T, const double (*lp)[3], const 
     return term;
 }
 
+__device__ __forceinline__ void grasp_rotation(const double *R9, const double *eeR, double *Ree);
+
+// ---- the held object (mppi_set_held_object_avoidance, mppi_set_held_object) -----------------------
+// Up to four spheres fixed in the grasp frame and the segments between consecutive ones
+// (include/mppi_amd.h has the definition).  Held point i sits at h_i = p_ee + Ree c_i, p_ee the
+// grasp-frame position that obstacle point 8 reads and Ree = R9 ee_R at the same lagged configuration
+// (grasp_rotation); every operation of the sum is rounded by itself.  The four points are formed once
+// per step; the table's reads - the object, the masks, the radii - are the wave's.
+// HP: a pointer to the DevHeld (the table's, in the table's address space, or a kernel argument's)
+template <typename HP>
+__device__ __forceinline__ void held_points(HP Hd, const double *pe, const double *Ree, double (*h)[3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < OB_HELD_POINTS; i++) {
+        const double cx = Hd->centres[i][0], cy = Hd->centres[i][1], cz = Hd->centres[i][2];
+#pragma unroll
+        for (int r = 0; r < 3; r++) h[i][r] = pe[r] + ((Ree[3 * r] * cx + Ree[3 * r + 1] * cy) + Ree[3 * r + 2] * cz);
+    }
+}
+
+// The tested unit u (wave-uniform): 0..3 the held points (the segment (h, h)), 4..6 the held segments,
+// each case by name so that the points stay in registers
+__device__ __forceinline__ void held_ends(const double (*h)[3], int u, double *a, double *b)
+{
+#define HELD_CASE(n, P, Q) case n: for (int i = 0; i < 3; i++) { a[i] = (P)[i]; b[i] = (Q)[i]; } break;
+    switch (u) {
+        HELD_CASE(0, h[0], h[0]) HELD_CASE(1, h[1], h[1]) HELD_CASE(2, h[2], h[2]) HELD_CASE(3, h[3], h[3])
+        HELD_CASE(4, h[0], h[1]) HELD_CASE(5, h[1], h[2])
+        default: for (int i = 0; i < 3; i++) { a[i] = h[2][i]; b[i] = h[3][i]; } break;
+    }
+#undef HELD_CASE
+}
+
+// The held points and segments against the table's obstacles: capsule_term's clearances, expression for
+// expression, with the held radii in place of the robot's.  Per obstacle, in order, the masked held
+// points in order (bits 9..12), then the masked held segments in order (bits 24..26); a bit that names a
+// point or segment the object does not have selects nothing.  Every mask test is a scalar branch.
+template <typename TP>
+__device__ __forceinline__ double held_obstacle_term(TP T, const double (*h)[3], int hc, double dt, int k)
+{
+    const double tau = __dsub_rn(__dadd_rn(T->t0, __dmul_rn((double)k, dt)), T->t_ref);
+    const int count = T->count;
+    const int n = count < OB_MAX ? count : OB_MAX;   // (never past the table, whatever it holds)
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    const unsigned pm = (1u << hc) - 1u, sm = (1u << (hc - 1)) - 1u;
+    double term = 0.0;
+#pragma unroll 1
+    for (int o = 0; o < n; o++) {
+        const unsigned mask = T->ob[o].mask;
+        const unsigned pb = (mask >> OB_HELD_POINT_BIT0) & pm, sb = (mask >> OB_HELD_SEGMENT_BIT0) & sm;
+        if ((pb | sb) == 0u) continue;
+        const double c0 = __dadd_rn(T->ob[o].position[0], __dmul_rn(T->ob[o].velocity[0], tau));
+        const double c1 = __dadd_rn(T->ob[o].position[1], __dmul_rn(T->ob[o].velocity[1], tau));
+        const double c2 = __dadd_rn(T->ob[o].position[2], __dmul_rn(T->ob[o].velocity[2], tau));
+        const int kind = T->ob[o].kind;
+        if (kind == OB_HALF_SPACE) {
+            const double n0 = T->ob[o].normal[0], n1 = T->ob[o].normal[1], n2 = T->ob[o].normal[2];
+#pragma unroll 1
+            for (int i = 0; i < OB_HELD_POINTS; i++) {
+                if ((pb >> i) & 1u) {
+                    double p[3], q[3];
+                    held_ends(h, i, p, q);
+                    const double v = ((n0 * (p[0] - c0) + n1 * (p[1] - c1)) + n2 * (p[2] - c2)) - T->held.radii[i];
+                    term += left_barrier(bound, scale, mx, v);
+                }
+            }
+#pragma unroll 1
+            for (int s = 0; s < OB_HELD_SEGMENTS; s++) {
+                if ((sb >> s) & 1u) {
+                    double p[3], q[3];
+                    held_ends(h, OB_HELD_POINTS + s, p, q);
+                    const double hp = (n0 * (p[0] - c0) + n1 * (p[1] - c1)) + n2 * (p[2] - c2);
+                    const double hq = (n0 * (q[0] - c0) + n1 * (q[1] - c1)) + n2 * (q[2] - c2);
+                    term += left_barrier(bound, scale, mx, ((hq < hp) ? hq : hp) - T->held.seg_radii[s]);
+                }
+            }
+        } else {
+            const bool cap = kind == OB_CAPSULE;
+            const double e0 = cap ? T->ob[o].normal[0] : 0.0, e1 = cap ? T->ob[o].normal[1] : 0.0, e2 = cap ? T->ob[o].normal[2] : 0.0;
+            const double E = dot3_rn(e0, e1, e2, e0, e1, e2);
+            const double ro = T->ob[o].radius;
+#pragma unroll 1
+            for (int i = 0; i < OB_HELD_POINTS; i++) {
+                if ((pb >> i) & 1u) {
+                    double p[3], q[3];
+                    held_ends(h, i, p, q);
+                    // the point is the segment (p, p): s = 0, t = clamp(F / E), 0 with E = 0
+                    const double F = dot3_rn(e0, e1, e2, __dsub_rn(p[0], c0), __dsub_rn(p[1], c1), __dsub_rn(p[2], c2));
+                    const double t = (E == 0.0) ? 0.0 : clamp01(__ddiv_rn(F, E));
+                    const double d0 = p[0] - __dadd_rn(c0, __dmul_rn(t, e0)), d1 = p[1] - __dadd_rn(c1, __dmul_rn(t, e1));
+                    const double d2 = p[2] - __dadd_rn(c2, __dmul_rn(t, e2));
+                    const double v = sqrt((d0 * d0 + d1 * d1) + d2 * d2) - (T->held.radii[i] + ro);
+                    term += left_barrier(bound, scale, mx, v);
+                }
+            }
+#pragma unroll 1
+            for (int s = 0; s < OB_HELD_SEGMENTS; s++) {
+                if ((sb >> s) & 1u) {
+                    double a[3], b[3];
+                    held_ends(h, OB_HELD_POINTS + s, a, b);
+                    const double d = segment_distance(a, b, c0, c1, c2, e0, e1, e2, E);
+                    term += left_barrier(bound, scale, mx, d - (T->held.seg_radii[s] + ro));
+                }
+            }
+        }
+    }
+    return term;
+}
+
+// The held points and segments in the distance field: field_term's sample, operation for operation -
+// the masked held points in order (the field's mask bits 9..12), then the masked held segments in order
+// (bits 24..26), each at its `samples` interior points in order j.  One rolled loop around one copy of
+// the sample; the corner loads are the only per-lane memory reads.  No field: nothing is read.
+template <typename TP>
+__device__ __forceinline__ double held_field_term(TP T, const double (*h)[3], int hc)
+{
+#pragma clang fp contract(off)
+    if (T->field.grid == nullptr) return 0.0;
+    const FieldGrid grid = (FieldGrid) reinterpret_cast<uint64_t>(T->field.grid);
+    const int nz = T->field.dims[2], nyz = T->field.dims[1] * nz;
+    const unsigned mask = T->field.mask;
+    int m = T->field.samples;
+    m = m < 0 ? 0 : (m > OB_FIELD_SAMPLES ? OB_FIELD_SAMPLES : m);   // (never past phi, whatever the table holds)
+    const unsigned pm = (1u << hc) - 1u, sm = (1u << (hc - 1)) - 1u;
+    // the units left: bits 0..3 the held points, bits 4..6 the held segments (none with no samples)
+    unsigned rem = ((mask >> OB_HELD_POINT_BIT0) & pm) | (m > 0 ? ((mask >> OB_HELD_SEGMENT_BIT0) & sm) << OB_HELD_POINTS : 0u);
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    double term = 0.0;
+#pragma unroll 1
+    while (rem) {
+        const int u = __builtin_ctz(rem);
+        rem &= rem - 1u;
+        const bool seg = u >= OB_HELD_POINTS;
+        const int cnt = seg ? m : 1;
+        double a[3], b[3];
+        held_ends(h, u, a, b);
+        const double rad = seg ? T->held.seg_radii[u - OB_HELD_POINTS] : T->held.radii[seg ? 0 : u];
+#pragma unroll 1
+        for (int j = 0; j < cnt; j++) {
+            const double phi = seg ? T->field.phi[j] : 0.0;
+            double p[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) p[i] = seg ? a[i] + phi * (b[i] - a[i]) : a[i];   // (a point is itself)
+            const FieldCell cell = field_cell(T, p);
+            const FieldGrid g = grid + cell.idx;
+            FieldGrid g1 = g + 1;
+            asm("" : "+v"(g1));   // (eight dword loads, as field_term's)
+            const float c0 = g[0], c1 = g1[0], c2 = g[nz], c3 = g1[nz], c4 = g[nyz], c5 = g1[nyz], c6 = g[nyz + nz], c7 = g1[nyz + nz];
+            const double z00 = field_lerp((double)c0, (double)c1, cell.f[2]), z01 = field_lerp((double)c2, (double)c3, cell.f[2]);
+            const double z10 = field_lerp((double)c4, (double)c5, cell.f[2]), z11 = field_lerp((double)c6, (double)c7, cell.f[2]);
+            const double y0 = field_lerp(z00, z01, cell.f[1]), y1 = field_lerp(z10, z11, cell.f[1]);
+            const double D = field_lerp(y0, y1, cell.f[0]);
+            const double bv = left_barrier(bound, scale, mx, D - rad);
+            term += cell.st == 0 ? bv : (cell.st == 1 ? 0.0 : __builtin_nan(""));
+        }
+    }
+    return term;
+}
+
+// The step's held term: the obstacles' part, then the field's.  Nothing held: +0.0, and nothing but
+// the object's count is read.
+template <typename TP>
+__device__ __forceinline__ double held_term_at(TP T, const double *pe, const double *Ree, double dt, int k)
+{
+    int hc = T->held.count;
+    hc = hc > OB_HELD_POINTS ? OB_HELD_POINTS : hc;   // (never past the object, whatever the table holds)
+    if (hc <= 0) return 0.0;
+    double h[OB_HELD_POINTS][3];
+    held_points(&T->held, pe, Ree, h);
+    return held_obstacle_term(T, h, hc, dt, k) + held_field_term(T, h, hc);
+}
+// ... from body 9's rotation where link_fk leaves it (R9) and the model's grasp placement
+template <typename TP>
+__device__ __forceinline__ double held_term(TP T, const double *pe, const double *R9, const double *eeR, double dt, int k)
+{
+    if (T->held.count <= 0) return 0.0;
+    double Ree[9];
+    grasp_rotation(R9, eeR, Ree);
+    return held_term_at(T, pe, Ree, dt, k);
+}
+
 // An update's obstacle table as the rollouts' objective reads it: nothing writes it during a launch
 // (obstacle_table_kernel ran before), so it is addressed in the constant address space, and its
 // address is made the wave's by v_readfirstlane - it is the same on every lane, but where it hangs
@@ -515,9 +697,11 @@ struct ObstacleRef {
 };
 // TERM: OB_TERM_POINTS obstacle_term, OB_TERM_CAPSULES capsule_term, OB_TERM_FIELD capsule_term and then
 // field_term, both from the same table - the folded filter() row's second pass so reads its own
-// update's grid
+// update's grid; OB_TERM_HELD (capsule_term + field_term) + held_term, the held object's from the same table
+// too, with body 9's rotation R9 and the model's grasp placement eeR
 template <int TERM = OB_TERM_POINTS>
-__device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt)
+__device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt,
+                                                const double *R9 = nullptr, const double *eeR = nullptr)
 {
     double term = 0.0;
     const int np = ob.ftab ? 2 : 1;
@@ -525,7 +709,8 @@ __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const dou
     for (int pass = 0; pass < np; pass++) {
         const ObstacleTableK T = pass ? ob.ftab : ob.tab;
         double t;
-        if constexpr (TERM == OB_TERM_FIELD) t = capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee);
+        if constexpr (TERM == OB_TERM_HELD) t = (capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee)) + held_term(T, ee, R9, eeR, dt, ob.k);
+        else if constexpr (TERM == OB_TERM_FIELD) t = capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee);
         else if constexpr (TERM == OB_TERM_CAPSULES) t = capsule_term(T, lp, ee, dt, ob.k);
         else t = obstacle_term(T, lp, ee, dt, ob.k);
         term = (pass == 0 || ob.frow) ? t : term;
@@ -618,7 +803,8 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 // OB (with LP): the obstacle term on the same link positions (ob: obstacle_cost), added after the
 // reference's terms; the link FK then runs whether or not the self-collision switch is on.  OB_TERM_NONE,
 // OB_TERM_POINTS (the nine points), OB_TERM_CAPSULES (points and segments, capsule obstacles) or
-// OB_TERM_FIELD (the capsule term and the distance field's)
+// OB_TERM_FIELD (the capsule term and the distance field's), or OB_TERM_HELD (those two and the held
+// object's, which needs body 9's rotation from the same link FK)
 template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
                                                              const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
@@ -726,10 +912,14 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
         double qj[10], lp[SC_LINKS][3];
 #pragma unroll
         for (int j = 0; j < 10; j++) qj[j] = lagged_q(pq[2 * j], pq[2 * j + 1], lm.dt, first);
-        link_fk(*lm.model, qj, lp);
+        double R9[OB == OB_TERM_HELD ? 9 : 1];   // body 9's rotation with the positions: the held object turns with the grasp
+        if constexpr (OB == OB_TERM_HELD) link_fk(*lm.model, qj, lp, R9);
+        else link_fk(*lm.model, qj, lp);
         double sct = 0.0;
         if (Cs.en_self) sct = self_collision_term<false>(Cs, lp);
-        const double obt = obstacle_cost<OB>(ob, lp, pe, lm.dt);
+        double obt;
+        if constexpr (OB == OB_TERM_HELD) obt = obstacle_cost<OB>(ob, lp, pe, lm.dt, R9, lm.model->ee_R);
+        else obt = obstacle_cost<OB>(ob, lp, pe, lm.dt);
         double cost = 0.0;
         cost += t_joint;
         cost += sct;
@@ -963,6 +1153,14 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
             double orient = 0.0;
             if (Cs.tp_track_orient) orient = record_orientation_term(src, tg, lm.model, &Cs, lm.dt, first);
             double lp[SC_LINKS][3];
+            if constexpr (OB == OB_TERM_HELD) {   // the held object turns with the grasp: body 9's rotation with the positions
+                double qj[10], R9[9];
+#pragma unroll
+                for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], lm.dt, first);
+                link_fk(*lm.model, qj, lp, R9);
+                return sc.gamma_k * (track_point_cost<true>(Cs, r, r[REC_QQD + 4], lp, tg, orient) +
+                                     obstacle_cost<OB>(ob, lp, r + REC_EE, lm.dt, R9, lm.model->ee_R));
+            }
             if (Cs.tp_en_self || OB) {
                 double qj[10];
 #pragma unroll

@@ -467,6 +467,14 @@ __global__ __launch_bounds__(64) void fr_object_field_kernel(const DevPinocchio 
     *out1 = mppi_cost::field_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION);
 }
 
+// mppi_dynamics_held_object_cost: the held term (held_term_at) at the grasp frame's cached pose - its
+// position and its rotation R9 ee_R as the last calculate() left them
+__global__ __launch_bounds__(64) void fr_object_held_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
+{
+    if (threadIdx.x != 0) return;
+    *out1 = mppi_cost::held_term_at(&t, obj->ee + MPPI_EE_POSITION, obj->ee + MPPI_EE_ROTATION, 0.0, 0);
+}
+
 // mppi_dynamics_target_cost: the target-tracking terms (fr_cost_terms.hpp track_point_cost) at the
 // grasp frame's cached pose - its position and its rotation R9 ee_R as the last calculate() left them
 __global__ __launch_bounds__(64) void fr_object_target_kernel(const DevPinocchio *obj, ObjTarget t, double *out2)
@@ -490,6 +498,12 @@ hipError_t launch_fr_object_target(const DevPinocchio *obj, const ObjTarget &t, 
 hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
 {
     hipLaunchKernelGGL(fr_object_field_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_object_held(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_object_held_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
     return hipGetLastError();
 }
 

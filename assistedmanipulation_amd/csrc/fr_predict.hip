@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "predict_plan.hpp"
 #include "fr_predict.hpp"
+#include "fr_cost_terms.hpp"
 
 using namespace mppi_eng;
 
@@ -80,9 +81,64 @@ __global__ __launch_bounds__(64) void fr_predict_kernel(const DevModel *model, c
     }
 }
 
+// The held points' world paths (mppi_predicted_held_optimal / mppi_predicted_held_rollouts): one thread
+// per (requested rollout, step), the same wave layout and NaN rule.  link_fk (fr_cost_terms.hpp) at the
+// record's q_k itself gives body 9's pose; the grasp frame sits at p9 + R9 ee_p with Ree = R9 ee_R, and
+// held point i at p_ee + Ree c_i as the cost terms form it.  Rows of points the object does not have are NaN.
+__global__ __launch_bounds__(64) void fr_predict_held_kernel(const DevModel *model, const double *rec, const PredictRow *rows, int H,
+                                                             DevHeld held, double *out)
+{
+    const int lane = threadIdx.x;
+    const PredictRow row = rows[blockIdx.x];
+    const int RS = row.compact ? FR_REC_C : FR_REC;
+    const double *rp = rec + row.offset;
+    double *op = out + (int64_t)blockIdx.x * H * (OB_HELD_POINTS * 3);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const int hc = held.count < 0 ? 0 : (held.count > OB_HELD_POINTS ? OB_HELD_POINTS : held.count);
+    int first_bad = 0x7fffffff;
+    for (int base = 0; base < H; base += 64) {
+        const int k = base + lane;
+        const bool act = k < H;
+        const double2 *r2 = reinterpret_cast<const double2 *>(rp + (int64_t)(act ? k : H - 1) * RS);
+        double q[FR_NB];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < FR_NB; j++) {
+            const double2 v = r2[REC_QQD / 2 + j];
+            q[j] = v.x;
+            ok = ok && finite64(v.x) && finite64(v.y);
+        }
+        const unsigned long long bad = __ballot(act && !ok);
+        if (first_bad == 0x7fffffff && bad) first_bad = base + __ffsll(bad) - 1;
+        if (!act) continue;   // (after the chunk's last wave-wide operation)
+        const bool dead = k >= first_bad;
+        double lp[SC_LINKS][3], R9[9], Ree[9], pe[3], hp[OB_HELD_POINTS][3];
+        mppi_cost::link_fk(*model, q, lp, R9);
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+            pe[r] = lp[SC_LINKS - 1][r] + ((R9[3 * r] * model->ee_p[0] + R9[3 * r + 1] * model->ee_p[1]) + R9[3 * r + 2] * model->ee_p[2]);
+        mppi_cost::grasp_rotation(R9, model->ee_R, Ree);
+        mppi_cost::held_points(&held, pe, Ree, hp);
+        double *o = op + (int64_t)k * (OB_HELD_POINTS * 3);
+#pragma unroll
+        for (int i = 0; i < OB_HELD_POINTS; i++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) o[3 * i + c] = (dead || i >= hc) ? nan : hp[i][c];
+    }
+}
+
 }  // namespace
 
 namespace mppi_eng {
+
+hipError_t launch_fr_predict_held(const DevModel *model, const double *rec, const PredictRow *rows, int64_t n, int H,
+                                  const DevHeld &held, double *out, hipStream_t s)
+{
+    if (n <= 0 || H <= 0) return hipSuccess;
+    if (n > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fr_predict_held_kernel, dim3((unsigned)n), dim3(64), 0, s, model, rec, rows, H, held, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_fr_predict(const DevModel *model, const double *rec, const PredictRow *rows, int64_t n, int H, int energy,
                              double *out, hipStream_t s)

@@ -24,6 +24,11 @@ struct PredictRow {
 hipError_t launch_fr_predict(const DevModel *model, const double *rec, const PredictRow *rows, int64_t n, int H, int energy,
                              double *out, hipStream_t s);
 
+// out[n][H][OB_HELD_POINTS][3]: the held points' world positions at q_k (mppi_predicted_held_*), NaN rows
+// for the points `held` does not have
+hipError_t launch_fr_predict_held(const DevModel *model, const double *rec, const PredictRow *rows, int64_t n, int H,
+                                  const DevHeld &held, double *out, hipStream_t s);
+
 // World translations of every body frame (lp[1 + i]: body i; lp[0]: the universe) and of the grasp
 // and arm-mount frames at joint positions q[0..11]: link_fk's chain (fr_cost_terms.hpp), pose_i =
 // pose_parent o placement_i o joint_i term for term with the rollout kernel's fsincos, carried past

@@ -210,6 +210,23 @@ class PinocchioDynamicsObject:
                                                               C.byref(v)))
         return v.value
 
+    def held_object_cost(self, config, obstacles, elapsed, field, held):
+        """mppi_dynamics_held_object_cost: the held term (Trajectory.set_held_object) of `held` (a
+        HeldObject or None) at the grasp pose the object cached at its last call, against `obstacles`
+        moved by `elapsed` seconds (their held mask bits) and against `field` (a DistanceField or None),
+        with `config`'s limit (None: the defaults)."""
+        from .obstacles import ObstacleAvoidance, obstacles_to_c
+        c = (config or ObstacleAvoidance()).to_c()
+        arr, n = obstacles_to_c(obstacles or [])
+        f = field.to_c() if field is not None else None
+        o = held.to_c() if held is not None else None
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_dynamics_held_object_cost(self._h, C.byref(c), arr, n, float(elapsed),
+                                                           C.byref(f) if f is not None else None,
+                                                           field.values_ptr() if field is not None else None,
+                                                           C.byref(o) if o is not None else None, C.byref(v)))
+        return v.value
+
     def obstacle_cost(self, config, obstacles, elapsed):
         """mppi_dynamics_obstacle_cost: the obstacle term (Trajectory.set_obstacle_avoidance) of
         `obstacles` moved by `elapsed` seconds, at the link and end-effector positions the object

@@ -428,6 +428,59 @@ class Trajectory:
         self._check(self._L.mppi_optimal_field_cost(self._h, C.byref(v)))
         return v.value
 
+    def set_held_object_avoidance(self):
+        """mppi_set_held_object_avoidance: a held object (spheres fixed in the grasp frame) in the
+        obstacle term, behind the field term.  After set_distance_field_avoidance and before the first
+        update; it cannot be undone."""
+        self._check(self._L.mppi_set_held_object_avoidance(self._h))
+
+    @property
+    def held_object_avoidance(self):
+        on = C.c_int(0)
+        self._check(self._L.mppi_get_held_object_avoidance(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_held_object(self, obj):
+        """mppi_set_held_object: replace the object (a HeldObject; None: it was put down).  Between
+        any two updates; every rank of a sharded run sets the same one."""
+        if obj is None:
+            self._check(self._L.mppi_set_held_object(self._h, None))
+        else:
+            o = obj.to_c()
+            self._check(self._L.mppi_set_held_object(self._h, C.byref(o)))
+
+    @property
+    def held_object(self):
+        """The current HeldObject (mppi_get_held_object), or None with nothing held."""
+        o, on = abi.mppi_held_object(), C.c_int(0)
+        self._check(self._L.mppi_get_held_object(self._h, C.byref(o), C.byref(on)))
+        if not on.value:
+            return None
+        from .held_object import HeldObject
+        return HeldObject.from_c(o)
+
+    def get_optimal_held_cost(self):
+        """mppi_optimal_held_cost: the held term of the last update's filter() row summed over its
+        steps, undiscounted (get_optimal_obstacle_cost holds it too, beside the capsule and field terms)."""
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_optimal_held_cost(self._h, C.byref(v)))
+        return v.value
+
+    def predicted_held_optimal(self):
+        """mppi_predicted_held_optimal: where the held points go under the published plan, (H, 4, 3)
+        world positions at q_k itself (not lagged); the rows of points the object does not have are NaN."""
+        raw = np.zeros((self.H, abi.MPPI_HELD_POINTS, 3))
+        self._check(self._L.mppi_predicted_held_optimal(self._h, _p(raw)))
+        return raw
+
+    def predicted_held_rollouts(self, indices):
+        """mppi_predicted_held_rollouts: the same for rollouts of the last update by global index,
+        (n, H, 4, 3) in the order of `indices`."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        raw = np.zeros((idx.size, self.H, abi.MPPI_HELD_POINTS, 3))
+        self._check(self._L.mppi_predicted_held_rollouts(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, _p(raw)))
+        return raw
+
     def set_obstacles(self, obstacles, time):
         """mppi_set_obstacles: replace the whole set (SphereObstacle / HalfSpaceObstacle, at most 16;
         an empty list clears it), given at reference time `time`.  Between any two updates; every

@@ -566,6 +566,77 @@ mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *f
 mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, int *present);
 mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost);
 
+/* A held object (mppi_set_held_object_avoidance): what the gripper carries - a beam, a tray, a tool -
+ * as spheres fixed in the grasp frame, one more part of the obstacle term behind the field term.
+ *
+ * The object is count in [0, MPPI_HELD_POINTS] spheres with centres c_i in the grasp frame, in metres,
+ * and radii r_i >= 0.  For count >= 2 there are segments s = 0 .. count - 2: segment s joins held point
+ * s and held point s + 1 and has its own radius segment_radii[s] >= 0 (a beam: two points and one
+ * segment; a tray: about four points and three segments; a tool tip: one point).  Coincident points (a
+ * zero-length segment) are legal and behave as a point, as robot segments 1 and 5 do.
+ * World position at the cost of step k:  h_i = p_ee + Ree c_i, with p_ee the grasp-frame position that
+ * obstacle point 8 reads and Ree = R9 ee_R (body 9's world rotation times the grasp placement's) taken at
+ * the same lagged configuration (q_0 for k = 0, q_{k-1} after).  Row r is
+ *   h_i[r] = p_ee[r] + ((Ree[r][0] c_x + Ree[r][1] c_y) + Ree[r][2] c_z)
+ * every operation rounded by itself (no fused multiply-add).  A non-finite pose makes the term NaN, and
+ * so the rollout, like any step cost.
+ * Clearances are the robot's own formulas (above) with the held radii in place of radii[i] and
+ * segment_radii[s]: a held point against a sphere, a half-space and a capsule; a held segment against a
+ * sphere or a capsule through the one segment-segment distance d(a, b; c, e); a held segment against a
+ * half-space by the minimum of its two ends; against the distance field D(h_i) - r_i for a point and,
+ * for a segment, its segment_samples interior samples p = h_s + phi_j (h_{s+1} - h_s), phi_j = j / (m + 1),
+ * with D(p) - segment_radii[s].  Each clearance goes through the avoidance configuration's Left(limit).
+ * Mask bits, in an obstacle's mask and in the field's: held point i is bit 9 + i
+ * (MPPI_OBSTACLE_MASK_HELD_POINT(i), i < 4), held segment s is bit 24 + s
+ * (MPPI_OBSTACLE_MASK_HELD_SEGMENT(s), s < 3), MPPI_OBSTACLE_MASK_HELD is all seven.  A bit that names a
+ * point or segment the current object does not have selects nothing; it is not an error, so one mask
+ * constant serves every object.  MPPI_OBSTACLE_MASK_ALL and MPPI_OBSTACLE_MASK_SEGMENTS keep their
+ * values: a set written for a robot without a held object means exactly what it meant.
+ * Order: the held term of a step runs over the obstacles in index order, per obstacle the masked held
+ * points in index order, then the masked held segments in index order; then, with a field present, the
+ * masked held points, then the masked held segments' samples in order j.  The step's obstacle term is
+ * (capsule term + field term) + held term, in that association.  With no object, or with nothing
+ * masked, the held term is +0.0 and every cost keeps its bits.  It acts wherever the obstacle term acts.
+ *
+ * mppi_set_held_object_avoidance selects the held-object kernels for the handle's life: after
+ * mppi_set_distance_field_avoidance and before the first update (MPPI_ERR_INVALID otherwise, the
+ * message says which).  mppi_set_held_object replaces the object between any two updates (NULL or
+ * count = 0: the object was put down).  MPPI_ERR_INVALID when the mode is off, count is outside [0, 4],
+ * a centre or a radius is not finite, or a radius is negative (of the points and segments the object
+ * has); a refused call leaves the object in place.  Not to be called concurrently with an update; on
+ * sharded handles every rank sets the same object.  On a held handle mppi_set_obstacles and
+ * mppi_set_distance_field accept the held bits; on every other handle they refuse them.  The filter()
+ * row of an update reads that update's object, also when the object was replaced before the row ran;
+ * captured graphs see each update's object.
+ * mppi_get_held_object: present = 0 with no object (out untouched).
+ * mppi_optimal_held_cost: the held term of the last filter() row summed over its steps, undiscounted (0
+ * with no object or before the first published update; MPPI_ERR_UNSUPPORTED on a handle without the
+ * mode); mppi_optimal_obstacle_cost returns capsule + field + held on a held handle.
+ * mppi_predicted_held_optimal / mppi_predicted_held_rollouts: the world paths of the held points at q_k
+ * itself (not lagged), as mppi_predicted_optimal / mppi_predicted_rollouts give the robot's:
+ * out[k][i][0..2] with MPPI_HELD_POINTS rows a step; the rows of points the current object does not
+ * have are NaN, and so is everything from a rollout's first non-finite step on.  The same error rules.
+ * Added like the field symbols, without a version change: detect by symbol. */
+#define MPPI_HELD_POINTS 4
+#define MPPI_HELD_SEGMENTS 3
+#define MPPI_OBSTACLE_MASK_HELD_POINT(i) (1u << (9 + (i)))
+#define MPPI_OBSTACLE_MASK_HELD_SEGMENT(s) (1u << (24 + (s)))
+#define MPPI_OBSTACLE_MASK_HELD 0x07001E00u
+typedef struct mppi_held_object {
+    int32_t count;
+    int32_t pad;
+    double centres[MPPI_HELD_POINTS][3];
+    double radii[MPPI_HELD_POINTS];
+    double segment_radii[MPPI_HELD_SEGMENTS];
+} mppi_held_object;
+mppi_status mppi_set_held_object_avoidance(mppi_handle *h);
+mppi_status mppi_get_held_object_avoidance(mppi_handle *h, int *enabled);
+mppi_status mppi_set_held_object(mppi_handle *h, const mppi_held_object *object);
+mppi_status mppi_get_held_object(mppi_handle *h, mppi_held_object *out, int *present);
+mppi_status mppi_optimal_held_cost(mppi_handle *h, double *cost);
+mppi_status mppi_predicted_held_optimal(mppi_handle *h, double *out_Hx4x3);
+mppi_status mppi_predicted_held_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out_nxHx4x3);
+
 /* Target tracking: TrackPoint follows a timed end-effector pose path over the horizon instead of
  * one fixed point.  The reference describes such targets (controller/trajectory.hpp) but feeds none
  * to an objective; here they are an opt-in mode of TrackPoint.  Nothing changes unless it is enabled.
@@ -902,6 +973,15 @@ mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_con
 mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
                                               const mppi_capsule_config *capsules, const mppi_distance_field *field,
                                               const float *values, double *cost);
+/* The held term (mppi_set_held_object_avoidance above) of `object` at the object's cached grasp-frame
+ * pose after its last call - its position and its rotation R9 ee_R - against `obstacles` at tau = elapsed
+ * (held mask bits legal, the robot's bits ignored) and, with `field` not NULL, against the field, with
+ * `config`'s limit (NULL: the defaults).  object NULL or count = 0: 0.  Stateless, the grid uploaded on
+ * every call - a diagnostic path.  Works in either link-position mode: the object caches the frame's
+ * pose in both. */
+mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
+                                           int32_t count, double elapsed, const mppi_distance_field *field, const float *values,
+                                           const mppi_held_object *object, double *cost);
 /* The target-tracking terms (mppi_set_target_tracking above) at the object's cached grasp-frame pose
  * after its last call: out2[0] = 100 pow(|p_EE - point|, 2), out2[1] = orientation_weight *
  * (3 - sum_ij Rt_ij Ree_ij) for `quaternion` (x, y, z, w; finite, norm in [0.5, 2], normalised here)

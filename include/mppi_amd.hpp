@@ -166,6 +166,38 @@ struct Configuration {
     unsigned int threads = 1;
 };
 
+// What the gripper carries (mppi_set_held_object): up to MPPI_HELD_POINTS spheres with centres in the
+// grasp frame, in metres, and the segments between consecutive ones.  segment_radii: one per segment
+// (centres.size() - 1 of them; missing ones are 0).
+struct HeldObject {
+    std::vector<std::array<double, 3>> centres;
+    std::vector<double> radii;
+    std::vector<double> segment_radii;
+
+    // the C struct; a size that does not fit reaches the engine's own check (count out of range)
+    mppi_held_object to_c() const
+    {
+        mppi_held_object o{};
+        o.count = (int32_t)centres.size();
+        for (size_t i = 0; i < centres.size() && i < (size_t)MPPI_HELD_POINTS; i++) {
+            for (int a = 0; a < 3; a++) o.centres[i][a] = centres[i][(size_t)a];
+            o.radii[i] = i < radii.size() ? radii[i] : 0.0;
+        }
+        for (size_t s = 0; s + 1 < centres.size() && s < (size_t)MPPI_HELD_SEGMENTS; s++) o.segment_radii[s] = s < segment_radii.size() ? segment_radii[s] : 0.0;
+        return o;
+    }
+    static HeldObject from_c(const mppi_held_object &o)
+    {
+        HeldObject h;
+        for (int i = 0; i < o.count && i < MPPI_HELD_POINTS; i++) {
+            h.centres.push_back({o.centres[i][0], o.centres[i][1], o.centres[i][2]});
+            h.radii.push_back(o.radii[i]);
+        }
+        for (int s = 0; s + 1 < o.count && s < MPPI_HELD_SEGMENTS; s++) h.segment_radii.push_back(o.segment_radii[s]);
+        return h;
+    }
+};
+
 class Trajectory {
 public:
     struct Rollout {
@@ -340,6 +372,54 @@ public:
         double c = 0.0;
         if (mppi_optimal_field_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
         return c;
+    }
+    // A held object behind the field term (mppi_set_held_object_avoidance): after
+    // set_distance_field_avoidance, before the first update; false and a message on stderr otherwise.
+    bool set_held_object_avoidance()
+    {
+        if (mppi_set_held_object_avoidance(m_h) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    bool held_object_avoidance() const
+    {
+        int on = 0;
+        return mppi_get_held_object_avoidance(m_h, &on) == MPPI_OK && on != 0;
+    }
+    // the object (mppi_set_held_object; nullptr: it was put down), replaced between any two updates
+    bool set_held_object(const HeldObject *object)
+    {
+        mppi_held_object o{};
+        if (object) o = object->to_c();
+        if (mppi_set_held_object(m_h, object ? &o : nullptr) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    bool set_held_object(const HeldObject &object) { return set_held_object(&object); }
+    // the current object, or nothing
+    std::optional<HeldObject> held_object() const
+    {
+        mppi_held_object o{};
+        int on = 0;
+        if (mppi_get_held_object(m_h, &o, &on) != MPPI_OK || !on) return std::nullopt;
+        return HeldObject::from_c(o);
+    }
+    // the held term of the optimal rollout, summed over its steps (mppi_optimal_held_cost)
+    double get_optimal_held_cost()
+    {
+        double c = 0.0;
+        if (mppi_optimal_held_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
+        return c;
+    }
+    // the held points' world paths at q_k (mppi_predicted_held_optimal / _rollouts): MPPI_HELD_POINTS x 3
+    // doubles a step, NaN rows for the points the object does not have; H steps, and n x H in the order of
+    // `rollouts` (global indices)
+    std::vector<double> get_predicted_held_optimal() const { return fetch(mppi_predicted_held_optimal, (size_t)(m_H * MPPI_HELD_POINTS * 3)); }
+    std::vector<double> get_predicted_held_rollouts(const std::vector<int64_t> &rollouts) const
+    {
+        std::vector<double> v(rollouts.size() * (size_t)(m_H * MPPI_HELD_POINTS * 3));
+        check(mppi_predicted_held_rollouts(m_h, rollouts.data(), (int64_t)rollouts.size(), v.data()));
+        return v;
     }
     // the whole set, given at reference time `time` (mppi_set_obstacles): between any two updates
     bool set_obstacles(const std::vector<mppi_obstacle> &obstacles, double time)
@@ -706,6 +786,17 @@ public:
     {
         double c = 0.0;
         check(mppi_dynamics_distance_field_cost(object(), config, capsules, &field, values, &c));
+        return c;
+    }
+    // the held term of `held` at the grasp frame's cached pose (mppi_dynamics_held_object_cost): against
+    // `obstacles` moved by `elapsed` (their held mask bits) and, with `field`, against the field
+    double held_object_cost(const mppi::HeldObject &held, const std::vector<mppi_obstacle> &obstacles, double elapsed,
+                            const mppi_distance_field *field = nullptr, const float *values = nullptr,
+                            const mppi_obstacle_config *config = nullptr)
+    {
+        double c = 0.0;
+        const mppi_held_object o = held.to_c();
+        check(mppi_dynamics_held_object_cost(object(), config, obstacles.data(), (int32_t)obstacles.size(), elapsed, field, values, &o, &c));
         return c;
     }
     // the target-tracking terms at the grasp frame's cached pose (mppi_dynamics_target_cost): position,
