@@ -38,7 +38,9 @@ MPPI_NOISE_DEVICE_PHILOX = 0
 MPPI_NOISE_HOST_INJECTED = 1
 MPPI_INDEX_WIDE = 0
 MPPI_INDEX_COMPAT_UINT8 = 1
-MPPI_UPDATE_INFO_N = 14   # mppi_update_info slots (MPPI_INFO_*)
+MPPI_UPDATE_INFO_N = 15   # mppi_update_info slots (MPPI_INFO_*)
+# MPPI_INFO_FINISH_PATH: the kernel that finished the last update (-1: the fused point-mass launch)
+MPPI_FINISH_FLAT, MPPI_FINISH_SG, MPPI_FINISH_SG_GLOBAL = 0, 1, 2
 MPPI_DEBUG_RELAY_NO_SIGNAL = 1   # mppi_debug_inject: relay stage 1 never signals stage 2
 MPPI_DEBUG_GRAPH_INSTANTIATE_FAIL = 2   # mppi_debug_inject: the next graph captures fail to instantiate
 # EndEffectorState layout (MPPI_EE_*) and DynamicsForecast rows (MPPI_DF_*)

@@ -2616,6 +2616,7 @@ static mppi_status phase3_launch(mppi_handle *h, double *seq_out)
     // the previous update's optimal rollout reads d_U / d_x0_opt: wait for it before rewriting
     if (h->opt_state == mppi_handle::OPT_LAUNCHED) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_opt_done, 0));
     h->gargs.fin = finish_args(h);
+    h->info[MPPI_INFO_FINISH_PATH] = finish_path(h->gargs.fin);   // (a replayed graph holds the same kernel node)
     if (!h->graph_dry) HIP_TRY(launch_finish(h->gargs.fin, h->stream));
     h->safety_ran = h->safety_on;
     if (h->safety_on) {   // (never under graph_dry: graph_eligible)
@@ -3486,6 +3487,7 @@ static mppi_status update_pm_fused(mppi_handle *h, const double *state, double t
     h->info[MPPI_INFO_ROWS] = h->count;
     h->info[MPPI_INFO_HANDOVER] = -1;
     h->info[MPPI_INFO_FUSED_UPDATE] = 1;
+    h->info[MPPI_INFO_FINISH_PATH] = -1;   // no finish launch: pm_update_kernel's finisher block
     h->updated_once = true;
     h->phase_open = true;
     mppi_status st = phase3_wait(h, a.seq);

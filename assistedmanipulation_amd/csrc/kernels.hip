@@ -892,7 +892,9 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, int &sg_err)
         }
         __syncthreads();
     }
-    if (a.control_bound) {
+    // (a filter that threw left optimise() before the clip, mppi.cpp:423-447: U*_shifted keeps the
+    // unclipped gradient step, which an update without a shift then builds on)
+    if (a.control_bound && !sg_err) {
         for (int t = threadIdx.x; t < HC; t += blockDim.x) {
             const int c = t % a.C;
             double u = a.Ushift[t];
@@ -1188,7 +1190,9 @@ __global__ __launch_bounds__(1024) void sg_finish_kernel(FinishArgs a)
         }
     }
     __syncthreads();
-    if (upd && a.control_bound) {
+    // (a filter that threw left optimise() before the clip, mppi.cpp:423-447: U*_shifted keeps the
+    // unclipped gradient step, which an update without a shift then builds on)
+    if (upd && a.control_bound && !sg_err) {
         for (int i = t; i < HC; i += blockDim.x) {
             const int cc = i % C;
             a.Ushift[i] = smax(smin(a.Ushift[i], a.cmax[cc]), a.cmin[cc]);
@@ -1301,15 +1305,30 @@ int graph_kernel_kind(const void *f)
     return GK_OTHER;
 }
 
-hipError_t launch_finish(const FinishArgs &a, hipStream_t s)
+// sg_finish_kernel's LDS: per dimension uu[W], tt[W], res[H]; then the 2w + 1 weights
+static size_t sg_finish_lds(const FinishArgs &a)
 {
     const int W = a.H + 2 * a.sg_window + 1;
-    const size_t lds = ((size_t)a.C * (2 * W + a.H) + 2 * a.sg_window + 1) * sizeof(double);
-    if (a.sg_window > 0 && W <= SGK_MAXW && a.C <= 16 && lds <= 65536) {
-        hipLaunchKernelGGL(sg_finish_kernel, dim3(1), dim3(64 * (a.C > 4 ? a.C : 4)), lds, s, a);
-    } else if (a.sg_window > 0) {
+    return ((size_t)a.C * (2 * W + a.H) + 2 * a.sg_window + 1) * sizeof(double);
+}
+
+int finish_path(const FinishArgs &a)
+{
+    if (a.sg_window <= 0) return MPPI_FINISH_FLAT;
+    const int W = a.H + 2 * a.sg_window + 1;
+    return (W <= SGK_MAXW && a.C <= 16 && sg_finish_lds(a) <= 65536) ? MPPI_FINISH_SG : MPPI_FINISH_SG_GLOBAL;
+}
+
+hipError_t launch_finish(const FinishArgs &a, hipStream_t s)
+{
+    switch (finish_path(a)) {
+    case MPPI_FINISH_SG:
+        hipLaunchKernelGGL(sg_finish_kernel, dim3(1), dim3(64 * (a.C > 4 ? a.C : 4)), sg_finish_lds(a), s, a);
+        break;
+    case MPPI_FINISH_SG_GLOBAL:
         hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, a);
-    } else {
+        break;
+    default:
         hipLaunchKernelGGL(finish_flat_kernel, dim3(1), dim3(1024), 0, s, a);
     }
     return hipGetLastError();

@@ -376,6 +376,8 @@ EnvSwitches env_switches_read();
 constexpr int FR_BODY_TABLE = 13 * 46;   // doubles of the cooperative kernels' body table (>= LDS_MODEL)
 hipError_t launch_fr_body_table(const DevModel *model, const DevCost *cost, double *table, hipStream_t s);
 hipError_t launch_finish(const FinishArgs &a, hipStream_t s);
+// The kernel launch_finish takes for these arguments (MPPI_FINISH_*: MPPI_INFO_FINISH_PATH reports it)
+int finish_path(const FinishArgs &a);
 // The kernel nodes of a captured update graph (engine.cpp update_graph) by their kernel function:
 // the ones whose arguments change per update (the rollout launches, the weight reduce, the finish,
 // the rank + next draws) and the rest (RCCL's, the gradient sum, the O(S log S) rank), which replay

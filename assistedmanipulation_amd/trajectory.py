@@ -786,14 +786,18 @@ class Trajectory:
         choices (cooperative kernel, folded filter(), objective in the launch, tail draws,
         sampling mode 0/1/2, rows rolled out, the step at which the fifth wave's rows moved off
         the doubled SIMD or -1, the in-launch waits that gave up in the last update - which then
-        failed - and summed since create)."""
+        failed - and summed since create; finish_path: the kernel that finished the update,
+        abi.MPPI_FINISH_*, -1 from the fused point-mass launch or a library without the slot)."""
         keys = ("cooperative", "folded_filter", "objective_in_launch", "tail_draws", "sampling", "rows", "handover",
                 "wait_timeouts", "wait_timeouts_total", "fused_update", "graph_updates", "graph_failures",
-                "update_count", "stage_work")
+                "update_count", "stage_work", "finish_path")
         out = np.zeros(abi.MPPI_UPDATE_INFO_N, dtype=np.int64)
-        st = self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
-        if st == abi.MPPI_ERR_INVALID:   # a library from before the stage_work slot takes one slot fewer
-            st = self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size - 1)
+        out[14] = -1
+        # a library from before the finish_path slot takes one slot fewer, one from before stage_work two
+        for n in (out.size, out.size - 1, out.size - 2):
+            st = self._L.mppi_update_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), n)
+            if st != abi.MPPI_ERR_INVALID:
+                break
         self._check(st)
         return {k: int(v) for k, v in zip(keys, out)}
 

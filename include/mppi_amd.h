@@ -846,7 +846,15 @@ mppi_status mppi_dims(mppi_handle *h, int64_t *rollouts_R, int64_t *steps_H,
 #define MPPI_INFO_STAGE_WORK 13           /* objective chunks that a later relay member's stage waves evaluated ahead
                                            * of their stage, counted on the device since create (0 with
                                            * MPPI_STAGE_WORK=0, one relay member, the tank or TrackPoint) */
-#define MPPI_UPDATE_INFO_N 14
+#define MPPI_INFO_FINISH_PATH 14          /* which kernel finished the last update (gradient step, Savitzky-Golay,
+                                           * clamp, publish): 0 finish_flat_kernel (no filter), 1 sg_finish_kernel
+                                           * (a wave per dimension, the window in LDS), 2 finish_kernel (a thread
+                                           * per dimension over global memory: windows sg_finish_kernel cannot
+                                           * stage); -1 when the fused point-mass launch finished it itself */
+#define MPPI_FINISH_FLAT 0
+#define MPPI_FINISH_SG 1
+#define MPPI_FINISH_SG_GLOBAL 2
+#define MPPI_UPDATE_INFO_N 15
 mppi_status mppi_update_info(mppi_handle *h, int64_t *info, int n);
 
 /* Fault injection for the failure-detection tests (no reference counterpart; never set in
