@@ -23,6 +23,7 @@ from .obstacles import (CapsuleObstacle, HalfSpaceObstacle, ObstacleAvoidance, O
                         segment_distance)
 from .distance_field import DistanceField, field_clearance  # noqa: E402
 from .held_object import HeldObject, MASK_HELD, held_object_clearance, mask_held_point, mask_held_segment  # noqa: E402
+from .held_self import HeldSelf, held_self_clearance, held_self_unit_point, held_self_unit_segment  # noqa: E402
 from .targets import TargetPath, TargetTracking, quaternion_rotation  # noqa: E402
 from .safety import TrajectorySafetyFilter  # noqa: E402
 from .csvlog import MPPILogger  # noqa: E402
@@ -38,5 +39,5 @@ __all__ = [
     "obstacle_clearance", "TrajectorySafetyFilter", "CapsuleObstacle", "ObstacleCapsules", "MASK_ALL", "MASK_SEGMENTS",
     "mask_segment", "obstacle_from_c", "obstacles_to_c", "segment_distance", "DistanceField", "field_clearance",
     "TargetPath", "TargetTracking", "quaternion_rotation", "HeldObject", "MASK_HELD", "mask_held_point", "mask_held_segment",
-    "held_object_clearance",
+    "held_object_clearance", "HeldSelf", "held_self_unit_point", "held_self_unit_segment", "held_self_clearance",
 ]

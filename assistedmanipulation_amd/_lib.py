@@ -141,6 +141,14 @@ PROTOTYPES = {
     "mppi_dynamics_held_object_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_obstacle), C.c_int32,
                                                  C.c_double, C.POINTER(abi.mppi_distance_field), C.POINTER(C.c_float),
                                                  C.POINTER(abi.mppi_held_object), _dp]),
+    "mppi_default_held_self": (None, [C.POINTER(abi.mppi_held_self)]),
+    "mppi_set_held_self_avoidance": (C.c_int, [_h]),
+    "mppi_get_held_self_avoidance": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "mppi_set_held_self": (C.c_int, [_h, C.POINTER(abi.mppi_held_self)]),
+    "mppi_get_held_self": (C.c_int, [_h, C.POINTER(abi.mppi_held_self), C.POINTER(C.c_int)]),
+    "mppi_optimal_held_self_cost": (C.c_int, [_h, _dp]),
+    "mppi_dynamics_held_self_cost": (C.c_int, [_h, C.POINTER(abi.mppi_obstacle_config), C.POINTER(abi.mppi_held_object),
+                                               C.POINTER(abi.mppi_held_self), _dp]),
 }
 
 _lib = None

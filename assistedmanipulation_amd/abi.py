@@ -229,6 +229,23 @@ class mppi_held_object(C.Structure):
                 ("segment_radii", _d * MPPI_HELD_SEGMENTS)]
 
 
+# mppi_set_held_self
+MPPI_HELD_SELF_UNITS = 0x7F
+MPPI_HELD_SELF_SEGMENTS = 8
+
+
+def MPPI_HELD_SELF_UNIT_POINT(i):
+    return 1 << i
+
+
+def MPPI_HELD_SELF_UNIT_SEGMENT(s):
+    return 1 << (4 + s)
+
+
+class mppi_held_self(C.Structure):
+    _fields_ = [("units", C.c_uint32), ("segments", C.c_uint32), ("radii", _d * MPPI_HELD_SELF_SEGMENTS)]
+
+
 class mppi_safety_filter_desc(C.Structure):
     """TrajectorySafetyFilter::Configuration (frankaridgeback/safety.hpp:15-40) -> include/mppi_amd.h."""
     _fields_ = [

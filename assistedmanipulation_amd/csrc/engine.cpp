@@ -241,6 +241,34 @@ mppi_held_object canonical_held(const mppi_held_object &o)
     return c;
 }
 
+// mppi_set_held_self's / mppi_dynamics_held_self_cost's configuration
+bool check_held_self(const mppi_held_self &c, std::string &why)
+{
+    if (c.units & ~MPPI_HELD_SELF_UNITS) {
+        why = "held self: units has bits above bit 6 (held points 0..3, held segments 4..6)";
+        return false;
+    }
+    if (c.segments & ~((1u << MPPI_HELD_SELF_SEGMENTS) - 1u)) {
+        why = "held self: segments has bits above bit 7";
+        return false;
+    }
+    for (int s = 0; s < MPPI_HELD_SELF_SEGMENTS; s++)
+        if (!std::isfinite(c.radii[s]) || c.radii[s] < 0.0) {
+            why = "held self: radii[" + std::to_string(s) + "] must be finite and >= 0";
+            return false;
+        }
+    return true;
+}
+
+// The table's fourth tail of a checked configuration
+void fill_held_self(DevHeldSelf &d, const mppi_held_self &c)
+{
+    d = DevHeldSelf{};
+    d.units = c.units;
+    d.segments = c.segments;
+    for (int s = 0; s < MPPI_HELD_SELF_SEGMENTS; s++) d.radii[s] = c.radii[s];
+}
+
 // mppi_set_obstacles' / mppi_dynamics_obstacle_cost's set (capsules: a capsule handle's, or
 // mppi_dynamics_capsule_cost's - the capsule kind and the segment bits of a mask are legal; held: a
 // held handle's, or mppi_dynamics_held_object_cost's - the held bits are legal too)
@@ -464,6 +492,10 @@ struct mppi_handle {
     // held); held_update: the object the last update ran with (mppi_predicted_held_*'s absent rows)
     bool held_avoidance = false, held_present = false;
     mppi_held_object held{}, held_update{};
+    // mppi_set_held_self_avoidance: the held-self kernels (FR_LINKS_HELD_SELF), fixed once enabled.
+    // mppi_set_held_self: the configuration the next update's table carries (held_self_present false: none)
+    bool held_self_avoidance = false, held_self_present = false;
+    mppi_held_self held_self{};
     // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
     // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
     // (phase3_launch).  safety_ran: the last phase 3 ran it (d_out_stage holds that update's
@@ -1419,6 +1451,36 @@ mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle
     return MPPI_OK;
 }
 
+mppi_status mppi_dynamics_held_self_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_held_object *object,
+                                         const mppi_held_self *self, double *cost)
+{
+    if (!d || !cost) return MPPI_ERR_INVALID;
+    if (d->link_positions != MPPI_LINK_POSITIONS_KINEMATIC)
+        return dfail(d, MPPI_ERR_INVALID, "held self cost needs the kinematic link-position model (mppi_dynamics_set_link_positions)");
+    mppi_obstacle_config c;
+    if (config) c = *config;
+    else mppi_default_obstacle_config(&c);
+    std::string why;
+    if (!check_obstacle_config(c, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (object && !check_held_object(*object, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (self && !check_held_self(*self, why)) return dfail(d, MPPI_ERR_INVALID, why);
+    if (!object || object->count == 0 || !self || self->units == 0u || self->segments == 0u) {   // nothing tested: no term
+        *cost = 0.0;
+        return MPPI_OK;
+    }
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    DHIP_TRY(hipSetDevice(d->device));
+    ObstacleTable t{};
+    fill_obstacle_table(t, c, nullptr, 0, 0.0, 0.0);
+    fill_held(t.held, *object);
+    fill_held_self(t.self, *self);
+    DHIP_TRY(launch_fr_object_held_self(d->d_obj, t, d->d_buf, d->stream));
+    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipStreamSynchronize(d->stream));
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
                                         double *out12)
 {
@@ -2174,6 +2236,7 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
 // FrRolloutArgs::link_positions of the handle's launches
 static int launch_link_mode(const mppi_handle *h)
 {
+    if (h->obstacle_avoidance && h->held_avoidance && h->held_self_avoidance) return FR_LINKS_HELD_SELF;
     if (h->obstacle_avoidance && h->held_avoidance) return FR_LINKS_HELD;
     if (h->obstacle_avoidance && h->field_avoidance) return FR_LINKS_FIELD;
     if (h->obstacle_avoidance) return h->obstacle_capsules ? FR_LINKS_CAPSULES : FR_LINKS_OBSTACLES;
@@ -2286,6 +2349,8 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
         h->held_update = h->held_present ? h->held : mppi_held_object{};
         fill_held(t.held, h->held_update);
     }
+    // (likewise the held-self configuration; none: the zeros the table starts with, nothing masked)
+    if (h->held_self_avoidance && h->held_self_present) fill_held_self(t.self, h->held_self);
     HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
     return MPPI_OK;
 }
@@ -3365,6 +3430,59 @@ mppi_status mppi_get_held_object(mppi_handle *h, mppi_held_object *out, int *pre
     return MPPI_OK;
 }
 
+void mppi_default_held_self(mppi_held_self *cfg)
+{
+    if (!cfg) return;
+    cfg->units = MPPI_HELD_SELF_UNITS;
+    cfg->segments = 0x1Fu;   // without the wrist and hand segments 5..7, which anything in the gripper touches
+    for (int s = 0; s < MPPI_HELD_SELF_SEGMENTS; s++) cfg->radii[s] = 0.1;
+}
+
+mppi_status mppi_set_held_self_avoidance(mppi_handle *h)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->held_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held self avoidance: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
+    // the held-self kernels are part of the launch plan and of a captured graph, like the held kernels
+    if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "held self avoidance is enabled before the first update");
+    h->held_self_avoidance = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_held_self_avoidance(mppi_handle *h, int *enabled)
+{
+    if (!h || !enabled) return MPPI_ERR_INVALID;
+    *enabled = h->held_self_avoidance ? 1 : 0;
+    return MPPI_OK;
+}
+
+mppi_status mppi_set_held_self(mppi_handle *h, const mppi_held_self *cfg)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    if (!h->held_self_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held self: held self avoidance is not enabled (mppi_set_held_self_avoidance)");
+    if (!cfg) {   // cleared: nothing is tested from the next update on
+        h->held_self_present = false;
+        return MPPI_OK;
+    }
+    std::string why;
+    if (!check_held_self(*cfg, why)) return fail(h, MPPI_ERR_INVALID, why);
+    // (host state only: the next update's table carries it, so a pending filter() row keeps its own)
+    h->held_self = *cfg;
+    h->held_self_present = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_held_self(mppi_handle *h, mppi_held_self *out, int *present)
+{
+    if (!h || !present) return MPPI_ERR_INVALID;
+    if (!h->held_self_avoidance)
+        return fail(h, MPPI_ERR_INVALID, "held self: held self avoidance is not enabled (mppi_set_held_self_avoidance)");
+    *present = h->held_self_present ? 1 : 0;
+    if (h->held_self_present && out) *out = h->held_self;
+    return MPPI_OK;
+}
+
 mppi_status mppi_set_graph(mppi_handle *h, int enable)
 {
     if (!h || enable < 0 || enable > 1) return MPPI_ERR_INVALID;
@@ -3663,11 +3781,15 @@ mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
     if (h->held_avoidance)   // a held handle: (capsule + field) + held
         HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 2,
                                      h->stream_opt));
-    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, (h->held_avoidance ? 3 : (h->field_avoidance ? 2 : 1)) * sizeof(double),
-                           hipMemcpyDeviceToHost, h->stream_opt));
+    if (h->held_self_avoidance)   // a held-self handle: ((capsule + field) + held) + self
+        HIP_TRY(launch_fr_held_self_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 3,
+                                          h->stream_opt));
+    const int parts = h->held_self_avoidance ? 4 : (h->held_avoidance ? 3 : (h->field_avoidance ? 2 : 1));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, parts * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->field_avoidance ? h->h_opt[1] + h->h_opt[2] : h->h_opt[1];
     if (h->held_avoidance) *cost += h->h_opt[3];
+    if (h->held_self_avoidance) *cost += h->h_opt[4];
     return MPPI_OK;
 }
 
@@ -3822,6 +3944,24 @@ mppi_status mppi_optimal_held_cost(mppi_handle *h, double *cost)
     // (the row's own update's table, and through it that update's object and grid)
     HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
                                  h->stream_opt));
+    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
+    HIP_TRY(hipStreamSynchronize(h->stream_opt));
+    *cost = h->h_opt[1];
+    return MPPI_OK;
+}
+
+mppi_status mppi_optimal_held_self_cost(mppi_handle *h, double *cost)
+{
+    if (!h || !cost) return MPPI_ERR_INVALID;
+    if (!h->held_self_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "held self cost: held self avoidance is not enabled");
+    HIP_TRY(hipSetDevice(h->device));
+    *cost = 0.0;
+    if (!h->published_once) return MPPI_OK;   // no filter() row yet
+    mppi_status st = wait_optimal(h);
+    if (st != MPPI_OK) return st;
+    // (the row's own update's table, and through it that update's object and configuration)
+    HIP_TRY(launch_fr_held_self_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
+                                      h->stream_opt));
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
     *cost = h->h_opt[1];

@@ -148,6 +148,15 @@ struct DevHeld {
     double radii[OB_HELD_POINTS];
     double seg_radii[OB_HELD_SEGMENTS];
 };
+// ... and, behind that, the held object against the robot's own segments (mppi_set_held_self_avoidance)
+constexpr int OB_TERM_HELD_SELF = 5;
+// The held-self configuration of one update: `units` bit i (i < 4) held point i, bit 4 + s held segment s;
+// `segments` bit s robot segment s (points s and s + 1) with radii[s], this term's own; both 0: nothing is tested.
+constexpr unsigned OB_HELD_SELF_UNITS = 0x7Fu, OB_HELD_SELF_SEGMENTS = 0xFFu;
+struct DevHeldSelf {
+    unsigned units, segments;
+    double radii[OB_SEGMENTS];
+};
 struct DevObstacle {
     double position[3], velocity[3], normal[3], radius;
     int kind;
@@ -162,6 +171,7 @@ struct ObstacleTable {
     double seg_radii[OB_SEGMENTS];   // capsule handles only (zeros otherwise)
     DevField field;                  // field handles only (zeros otherwise): behind everything the other kernels read
     DevHeld held;                    // held handles only (zeros otherwise): behind the field, so every older offset stays
+    DevHeldSelf self;                // held-self handles only (zeros otherwise): behind the held object, likewise
 };
 // the table's room behind the 2 H step-constant slots, in StepConst units
 constexpr int OB_TABLE_STEPS = (int)((sizeof(ObstacleTable) + sizeof(StepConst) - 1) / sizeof(StepConst));

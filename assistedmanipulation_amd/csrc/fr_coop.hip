@@ -33,16 +33,17 @@
 // one-step kinematic lag, NaN stop); only the association order of sums and products differs.
 // The rollout runs all H - 1 steps: a NaN step cost makes the rollout's sum NaN whatever follows.
 //
-// Units.  This text is compiled twelve times, once per cell of a 6 x 2 grid: -DFR_UNIT_LINKS=l,
-// the link mode FR_LINKS_ZERO .. FR_LINKS_HELD (FrRolloutArgs::link_positions: the reference's stub,
+// Units.  This text is compiled fourteen times, once per cell of a 7 x 2 grid: -DFR_UNIT_LINKS=l,
+// the link mode FR_LINKS_ZERO .. FR_LINKS_HELD_SELF (FrRolloutArgs::link_positions: the reference's stub,
 // the kinematic link-position objective, then the obstacle term on points, on segments and capsules,
-// with the distance field behind them, and with a held object behind that), and -DFR_UNIT_WR=w, the
+// with the distance field behind them, with a held object behind that, and with the held object against
+// the robot's own segments), and -DFR_UNIT_WR=w, the
 // simulated end-effector wrench in
 // the step off or on (FrRolloutArgs::simulated_wrench).  Both default to 0.  A unit holds its cell's
 // two kernels, named fr_coop_[x_][wr_]<links>kernel with <links> one of "", lp_, lp_ob_, lp_cap_,
-// lp_df_, lp_ho_, and their launchers, FrCoopUnit<l, w>'s members; cell (0, 0), the default unit, holds also
+// lp_df_, lp_ho_, lp_hs_, and their launchers, FrCoopUnit<l, w>'s members; cell (0, 0), the default unit, holds also
 // the table kernel and everything the host calls, which picks a unit from a table over the grid.  The
-// Makefile builds the twelve objects from one rule.  The kernels are units apart because in one unit they
+// Makefile builds the fourteen objects from one rule.  The kernels are units apart because in one unit they
 // changed each other's code: apart, a cell's instruction stream does not depend on the other cells.
 #ifndef FR_UNIT_LINKS
 #define FR_UNIT_LINKS 0
@@ -73,9 +74,10 @@ using mppi_dev::smax;
 using mppi_dev::smin;
 
 // the unit's cell, and what follows from it: the link-position objective, and its obstacle term
-static_assert(FR_UNIT_LINKS >= FR_LINKS_ZERO && FR_UNIT_LINKS <= FR_LINKS_HELD && (FR_UNIT_WR == 0 || FR_UNIT_WR == 1), "no such unit");
+static_assert(FR_UNIT_LINKS >= FR_LINKS_ZERO && FR_UNIT_LINKS <= FR_LINKS_HELD_SELF && (FR_UNIT_WR == 0 || FR_UNIT_WR == 1), "no such unit");
 static_assert(OB_TERM_NONE == 0 && FR_LINKS_OBSTACLES - 1 == OB_TERM_POINTS && FR_LINKS_CAPSULES - 1 == OB_TERM_CAPSULES &&
-                  FR_LINKS_FIELD - 1 == OB_TERM_FIELD && FR_LINKS_HELD - 1 == OB_TERM_HELD, "a link mode past the kinematic one is its obstacle term + 1");
+                  FR_LINKS_FIELD - 1 == OB_TERM_FIELD && FR_LINKS_HELD - 1 == OB_TERM_HELD &&
+                  FR_LINKS_HELD_SELF - 1 == OB_TERM_HELD_SELF, "a link mode past the kinematic one is its obstacle term + 1");
 constexpr bool UNIT_LP = FR_UNIT_LINKS != FR_LINKS_ZERO, UNIT_WR = FR_UNIT_WR != 0;
 constexpr int UNIT_OB = FR_UNIT_LINKS > FR_LINKS_KINEMATIC ? FR_UNIT_LINKS - 1 : OB_TERM_NONE;
 
@@ -2329,6 +2331,7 @@ __device__ __forceinline__ void block0_sample_writes(const FrRolloutArgs &a, int
 #define FR_LINKS_TAG_3 lp_cap_
 #define FR_LINKS_TAG_4 lp_df_
 #define FR_LINKS_TAG_5 lp_ho_
+#define FR_LINKS_TAG_6 lp_hs_
 #define FR_PASTE2_(a, b) a##b
 #define FR_PASTE2(a, b) FR_PASTE2_(a, b)
 #define FR_PASTE4_(a, b, c, d) a##b##c##d
@@ -2445,14 +2448,14 @@ constexpr std::array<std::array<UnitEntry, 2>, sizeof...(LINKS)> unit_table(std:
 {
     return {{{{unit_entry<LINKS, false>(), unit_entry<LINKS, true>()}}...}};
 }
-constexpr auto UNITS = unit_table(std::make_integer_sequence<int, FR_LINKS_HELD + 1>{});
+constexpr auto UNITS = unit_table(std::make_integer_sequence<int, FR_LINKS_HELD_SELF + 1>{});
 
-// The launch's unit.  The engine passes FR_LINKS_ZERO .. FR_LINKS_HELD (engine.cpp launch_link_mode);
+// The launch's unit.  The engine passes FR_LINKS_ZERO .. FR_LINKS_HELD_SELF (engine.cpp launch_link_mode);
 // any other value means the link-position objective alone, as every non-zero value short of an obstacle
 // mode does, and never indexes the table.
 static const UnitEntry &unit_of(const FrRolloutArgs &a)
 {
-    const int links = a.link_positions >= FR_LINKS_ZERO && a.link_positions <= FR_LINKS_HELD ? a.link_positions : FR_LINKS_KINEMATIC;
+    const int links = a.link_positions >= FR_LINKS_ZERO && a.link_positions <= FR_LINKS_HELD_SELF ? a.link_positions : FR_LINKS_KINEMATIC;
     return UNITS[links][a.simulated_wrench != 0];
 }
 

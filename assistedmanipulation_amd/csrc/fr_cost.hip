@@ -88,6 +88,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #include "fr_step_cost_kernel_body.inc"
 }
 
+// The same with the held object against the robot's own segments behind the held term (FR_LINKS_HELD_SELF:
+// fr_cost_terms.hpp held_self_term)
+template <int CK, bool EN, bool KC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_hs_kernel(FrCostArgs a)
+{
+    constexpr bool LP = true;
+    constexpr int OB = OB_TERM_HELD_SELF;
+#include "fr_step_cost_kernel_body.inc"
+}
+
 // An update's obstacle table from the launch's arguments into its place behind the step constants
 __global__ __launch_bounds__(64) void obstacle_table_kernel(ObstacleTable t, ObstacleTable *out)
 {
@@ -169,6 +179,30 @@ __global__ __launch_bounds__(64) void fr_held_total_kernel(const StepConst *step
         for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
         link_fk(*model, qj, lp, R9);
         const double t = held_term(T, r + REC_EE, R9, model->ee_R, dt, k);
+        for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
+    }
+    if (lane == 0) *out1 = tot;
+}
+
+// The held-self term of the filter() row the same way (mppi_optimal_held_self_cost), from the table - and
+// so the object and the configuration - of the row's own update.  (One wave a launch: the link and held
+// coordinates stay in registers through the pair loop, 256 VGPRs; bounded to its twin's three waves a SIMD it
+// spills 592 bytes a lane.)
+__global__ __launch_bounds__(64) void fr_held_self_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
+                                                                const DevModel *model, double dt, double *out1)
+{
+    const int lane = threadIdx.x;
+    const ObstacleTableK T = obstacle_table_of(steps, H);
+    double tot = 0.0;
+    for (int base = 0; base < H; base += 64) {
+        const int n = (H - base < 64) ? H - base : 64;
+        const int k = base + (lane < n ? lane : 0);
+        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);
+        double qj[10], lp[SC_LINKS][3], R9[9], Ree[9];
+        for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
+        link_fk(*model, qj, lp, R9);
+        grasp_rotation(R9, model->ee_R, Ree);
+        const double t = held_self_term_at(T, lp, r + REC_EE, Ree);
         for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
     }
     if (lane == 0) *out1 = tot;
@@ -295,13 +329,31 @@ hipError_t launch_fr_held_total(const StepConst *steps, const double *rec, int H
     return hipGetLastError();
 }
 
+hipError_t launch_fr_held_self_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                     double dt, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_held_self_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    return hipGetLastError();
+}
+
 hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s)
 {
     const int64_t rows = a.count + (a.fcost ? 1 : 0);
     if (rows == 0) return hipSuccess;
     const dim3 grid((unsigned)rows), block(64);
     // the records' layout is the launch's that wrote them (FrCostArgs::compact)
-    if (a.link_positions == FR_LINKS_HELD) {
+    if (a.link_positions == FR_LINKS_HELD_SELF) {
+        if (!a.model) return hipErrorInvalidValue;
+        if (a.compact) {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
+        } else {
+            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
+            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
+        }
+    } else if (a.link_positions == FR_LINKS_HELD) {
         if (!a.model) return hipErrorInvalidValue;
         if (a.compact) {
             if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);

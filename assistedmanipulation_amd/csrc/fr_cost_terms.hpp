@@ -652,17 +652,99 @@ __device__ __forceinline__ double held_field_term(TP T, const double (*h)[3], in
 
 // The step's held term: the obstacles' part, then the field's.  Nothing held: +0.0, and nothing but
 // the object's count is read.
+// h: the four world points, handed on to held_self_term (left alone where nothing is held)
 template <typename TP>
-__device__ __forceinline__ double held_term_at(TP T, const double *pe, const double *Ree, double dt, int k)
+__device__ __forceinline__ double held_term_at(TP T, const double *pe, const double *Ree, double dt, int k, double (*h)[3])
 {
     int hc = T->held.count;
     hc = hc > OB_HELD_POINTS ? OB_HELD_POINTS : hc;   // (never past the object, whatever the table holds)
     if (hc <= 0) return 0.0;
-    double h[OB_HELD_POINTS][3];
     held_points(&T->held, pe, Ree, h);
     return held_obstacle_term(T, h, hc, dt, k) + held_field_term(T, h, hc);
 }
-// ... from body 9's rotation where link_fk leaves it (R9) and the model's grasp placement
+template <typename TP>
+__device__ __forceinline__ double held_term_at(TP T, const double *pe, const double *Ree, double dt, int k)
+{
+    double h[OB_HELD_POINTS][3];
+    return held_term_at(T, pe, Ree, dt, k, h);
+}
+
+// ---- the held object against the robot's own segments (mppi_set_held_self_avoidance) ---------------
+// The units the step tests (wave-uniform): bits 0..3 the masked held points, bits 4..6 the masked held
+// segments, of those the current object has; 0 with no object, no configuration or no robot segment
+// masked - then nothing but the counts and masks was read.
+template <typename TP>
+__device__ __forceinline__ unsigned held_self_units(TP T)
+{
+    int hc = T->held.count;
+    hc = hc > OB_HELD_POINTS ? OB_HELD_POINTS : hc;
+    if (hc <= 0) return 0u;
+    if ((T->self.segments & OB_HELD_SELF_SEGMENTS) == 0u) return 0u;
+    const unsigned pm = (1u << hc) - 1u, sm = (1u << (hc - 1)) - 1u;
+    return T->self.units & (pm | (sm << OB_HELD_POINTS));
+}
+
+// The held units against the robot's segments (include/mppi_amd.h has the definition): capsule_term's
+// segment clearance with the robot's segment a -> b first and the held unit c -> c + e second - a held
+// point has e = 0, a held segment e = h_{s'+1} - h_s', one rounded subtraction a component - and
+// v = d - (self.radii[s] + r_u).  Units in order u = 0..6, per unit the masked robot segments in order
+// s = 0..7: two rolled loops around one copy of the distance; held_ends and segment_ends pick the ends by
+// name.  rem: held_self_units, not 0; h: the step's held points, as held_term_at formed them.
+template <typename TP>
+__device__ __forceinline__ double held_self_term(TP T, unsigned rem, const double (*h)[3], const double (*lp)[3], const double *ee)
+{
+    const unsigned segs = T->self.segments & OB_HELD_SELF_SEGMENTS;
+    const double bound = T->limit.bound, scale = T->limit.scale, mx = T->limit.max;
+    double term = 0.0;
+#pragma unroll 1
+    while (rem) {
+        const int u = __builtin_ctz(rem);
+        rem &= rem - 1u;
+        const bool seg = u >= OB_HELD_POINTS;
+        double c[3], q[3];
+        held_ends(h, u, c, q);
+        const double e0 = seg ? __dsub_rn(q[0], c[0]) : 0.0, e1 = seg ? __dsub_rn(q[1], c[1]) : 0.0, e2 = seg ? __dsub_rn(q[2], c[2]) : 0.0;
+        const double E = dot3_rn(e0, e1, e2, e0, e1, e2);
+        const double ru = seg ? T->held.seg_radii[u - OB_HELD_POINTS] : T->held.radii[seg ? 0 : u];
+        unsigned sl = segs;
+#pragma unroll 1
+        while (sl) {
+            const int s = __builtin_ctz(sl);
+            sl &= sl - 1u;
+            double a[3], b[3];
+            segment_ends(lp, ee, s, a, b);
+            const double d = segment_distance(a, b, c[0], c[1], c[2], e0, e1, e2, E);
+            term += left_barrier(bound, scale, mx, d - (T->self.radii[s] + ru));
+        }
+    }
+    return term;
+}
+
+// The step's held term and, behind it, its held-self term (self): the points are formed once for both
+template <typename TP>
+__device__ __forceinline__ double held_terms(TP T, const double (*lp)[3], const double *pe, const double *R9, const double *eeR,
+                                             double dt, int k, double &self)
+{
+    self = 0.0;
+    if (T->held.count <= 0) return 0.0;
+    double Ree[9], h[OB_HELD_POINTS][3];
+    grasp_rotation(R9, eeR, Ree);
+    const double held = held_term_at(T, pe, Ree, dt, k, h);
+    const unsigned rem = held_self_units(T);
+    if (rem) self = held_self_term(T, rem, h, lp, pe);
+    return held;
+}
+// The held-self term alone at a grasp pose (Ree) and link positions: the read-out's and the device object's
+template <typename TP>
+__device__ __forceinline__ double held_self_term_at(TP T, const double (*lp)[3], const double *pe, const double *Ree)
+{
+    const unsigned rem = held_self_units(T);
+    if (rem == 0u) return 0.0;
+    double h[OB_HELD_POINTS][3];
+    held_points(&T->held, pe, Ree, h);
+    return held_self_term(T, rem, h, lp, pe);
+}
+// held_term_at from body 9's rotation where link_fk leaves it (R9) and the model's grasp placement
 template <typename TP>
 __device__ __forceinline__ double held_term(TP T, const double *pe, const double *R9, const double *eeR, double dt, int k)
 {
@@ -698,7 +780,8 @@ struct ObstacleRef {
 // TERM: OB_TERM_POINTS obstacle_term, OB_TERM_CAPSULES capsule_term, OB_TERM_FIELD capsule_term and then
 // field_term, both from the same table - the folded filter() row's second pass so reads its own
 // update's grid; OB_TERM_HELD (capsule_term + field_term) + held_term, the held object's from the same table
-// too, with body 9's rotation R9 and the model's grasp placement eeR
+// too, with body 9's rotation R9 and the model's grasp placement eeR; OB_TERM_HELD_SELF that and then
+// held_self_term on the same held points, ((capsule + field) + held) + self
 template <int TERM = OB_TERM_POINTS>
 __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const double (*lp)[3], const double *ee, double dt,
                                                 const double *R9 = nullptr, const double *eeR = nullptr)
@@ -709,7 +792,12 @@ __device__ __forceinline__ double obstacle_cost(const ObstacleRef &ob, const dou
     for (int pass = 0; pass < np; pass++) {
         const ObstacleTableK T = pass ? ob.ftab : ob.tab;
         double t;
-        if constexpr (TERM == OB_TERM_HELD) t = (capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee)) + held_term(T, ee, R9, eeR, dt, ob.k);
+        if constexpr (TERM == OB_TERM_HELD_SELF) {
+            const double cf = capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee);
+            double self;
+            const double held = held_terms(T, lp, ee, R9, eeR, dt, ob.k, self);
+            t = (cf + held) + self;
+        } else if constexpr (TERM == OB_TERM_HELD) t = (capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee)) + held_term(T, ee, R9, eeR, dt, ob.k);
         else if constexpr (TERM == OB_TERM_FIELD) t = capsule_term(T, lp, ee, dt, ob.k) + field_term(T, lp, ee);
         else if constexpr (TERM == OB_TERM_CAPSULES) t = capsule_term(T, lp, ee, dt, ob.k);
         else t = obstacle_term(T, lp, ee, dt, ob.k);
@@ -804,7 +892,8 @@ __device__ __forceinline__ void derive_record(const double *rk, double *r, bool 
 // reference's terms; the link FK then runs whether or not the self-collision switch is on.  OB_TERM_NONE,
 // OB_TERM_POINTS (the nine points), OB_TERM_CAPSULES (points and segments, capsule obstacles) or
 // OB_TERM_FIELD (the capsule term and the distance field's), or OB_TERM_HELD (those two and the held
-// object's, which needs body 9's rotation from the same link FK)
+// object's, which needs body 9's rotation from the same link FK), or OB_TERM_HELD_SELF (those three and
+// the held object against the robot's segments)
 template <bool EN, int JS, bool KC = false, int JG = 1, bool LP = false, int OB = OB_TERM_NONE>
 __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, const StepConst &sc, const double *r,
                                                              const double *Lj, const double2 *src, LinkModel lm = LinkModel{},
@@ -912,13 +1001,13 @@ __device__ __forceinline__ double assisted_manipulation_cost(const DevCost &Cs, 
         double qj[10], lp[SC_LINKS][3];
 #pragma unroll
         for (int j = 0; j < 10; j++) qj[j] = lagged_q(pq[2 * j], pq[2 * j + 1], lm.dt, first);
-        double R9[OB == OB_TERM_HELD ? 9 : 1];   // body 9's rotation with the positions: the held object turns with the grasp
-        if constexpr (OB == OB_TERM_HELD) link_fk(*lm.model, qj, lp, R9);
+        double R9[OB >= OB_TERM_HELD ? 9 : 1];   // body 9's rotation with the positions: the held object turns with the grasp
+        if constexpr (OB >= OB_TERM_HELD) link_fk(*lm.model, qj, lp, R9);
         else link_fk(*lm.model, qj, lp);
         double sct = 0.0;
         if (Cs.en_self) sct = self_collision_term<false>(Cs, lp);
         double obt;
-        if constexpr (OB == OB_TERM_HELD) obt = obstacle_cost<OB>(ob, lp, pe, lm.dt, R9, lm.model->ee_R);
+        if constexpr (OB >= OB_TERM_HELD) obt = obstacle_cost<OB>(ob, lp, pe, lm.dt, R9, lm.model->ee_R);
         else obt = obstacle_cost<OB>(ob, lp, pe, lm.dt);
         double cost = 0.0;
         cost += t_joint;
@@ -1153,7 +1242,7 @@ __device__ __forceinline__ double step_cost(const DevCost &Cs, const StepConst &
             double orient = 0.0;
             if (Cs.tp_track_orient) orient = record_orientation_term(src, tg, lm.model, &Cs, lm.dt, first);
             double lp[SC_LINKS][3];
-            if constexpr (OB == OB_TERM_HELD) {   // the held object turns with the grasp: body 9's rotation with the positions
+            if constexpr (OB >= OB_TERM_HELD) {   // the held object turns with the grasp: body 9's rotation with the positions
                 double qj[10], R9[9];
 #pragma unroll
                 for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], lm.dt, first);

@@ -475,6 +475,14 @@ __global__ __launch_bounds__(64) void fr_object_held_kernel(const DevPinocchio *
     *out1 = mppi_cost::held_term_at(&t, obj->ee + MPPI_EE_POSITION, obj->ee + MPPI_EE_ROTATION, 0.0, 0);
 }
 
+// mppi_dynamics_held_self_cost: the held-self term (held_self_term_at) at the cached link positions and
+// the grasp frame's cached pose
+__global__ __launch_bounds__(64) void fr_object_held_self_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
+{
+    if (threadIdx.x != 0) return;
+    *out1 = mppi_cost::held_self_term_at(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, obj->ee + MPPI_EE_ROTATION);
+}
+
 // mppi_dynamics_target_cost: the target-tracking terms (fr_cost_terms.hpp track_point_cost) at the
 // grasp frame's cached pose - its position and its rotation R9 ee_R as the last calculate() left them
 __global__ __launch_bounds__(64) void fr_object_target_kernel(const DevPinocchio *obj, ObjTarget t, double *out2)
@@ -504,6 +512,12 @@ hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &
 hipError_t launch_fr_object_held(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
 {
     hipLaunchKernelGGL(fr_object_held_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_object_held_self(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fr_object_held_self_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
     return hipGetLastError();
 }
 

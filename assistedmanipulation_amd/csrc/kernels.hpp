@@ -124,7 +124,8 @@ struct FinishArgs {
 constexpr int FR_WRENCH_ROW = 8;
 static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows behind the step constants");
 // FrRolloutArgs / FrCostArgs::link_positions
-constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3, FR_LINKS_FIELD = 4, FR_LINKS_HELD = 5;
+constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3, FR_LINKS_FIELD = 4, FR_LINKS_HELD = 5,
+              FR_LINKS_HELD_SELF = 6;
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -178,6 +179,8 @@ struct FrRolloutArgs {
     // *_df_kernel units), the grid through the same table's second tail.
     // FR_LINKS_HELD: those two and the held object's (mppi_set_held_object_avoidance; the *_ho_kernel
     // units), the object in the same table's third tail.
+    // FR_LINKS_HELD_SELF: those three and the held object against the robot's own segments
+    // (mppi_set_held_self_avoidance; the *_hs_kernel units), the configuration in the table's fourth tail.
     int link_positions;
     CostStats *stats;
     // the next update's draws for the main waves' own rows, made in the launch's idle tail into
@@ -540,6 +543,11 @@ hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &
 hipError_t launch_fr_held_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
                                 double dt, double *out1, hipStream_t s);
 hipError_t launch_fr_object_held(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
+// The held-self term alone (mppi_set_held_self_avoidance) the same two ways: fr_held_self_total_kernel, and at
+// the object's cached link positions and grasp pose (mppi_dynamics_held_self_cost, fr_object_held_self_kernel)
+hipError_t launch_fr_held_self_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                     double dt, double *out1, hipStream_t s);
+hipError_t launch_fr_object_held_self(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
 
 // Target tracking (mppi_set_target_tracking, mppi_set_target_path): the timed pose path as the host
 // stored it - quaternions normalised and sign-fixed, inv[i] = 1 / (time[i + 1] - time[i]) - and the

@@ -227,6 +227,20 @@ class PinocchioDynamicsObject:
                                                            C.byref(o) if o is not None else None, C.byref(v)))
         return v.value
 
+    def held_self_cost(self, config, held, held_self):
+        """mppi_dynamics_held_self_cost: the held-self term (Trajectory.set_held_self) of `held` (a
+        HeldObject or None) under `held_self` (a HeldSelf or None) at the link positions and the grasp
+        pose the object cached at its last call, with `config`'s limit (None: the defaults).  Needs
+        kinematic link positions."""
+        from .obstacles import ObstacleAvoidance
+        c = (config or ObstacleAvoidance()).to_c()
+        o = held.to_c() if held is not None else None
+        f = held_self.to_c() if held_self is not None else None
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_dynamics_held_self_cost(self._h, C.byref(c), C.byref(o) if o is not None else None,
+                                                         C.byref(f) if f is not None else None, C.byref(v)))
+        return v.value
+
     def obstacle_cost(self, config, obstacles, elapsed):
         """mppi_dynamics_obstacle_cost: the obstacle term (Trajectory.set_obstacle_avoidance) of
         `obstacles` moved by `elapsed` seconds, at the link and end-effector positions the object

@@ -466,6 +466,44 @@ class Trajectory:
         self._check(self._L.mppi_optimal_held_cost(self._h, C.byref(v)))
         return v.value
 
+    def set_held_self_avoidance(self):
+        """mppi_set_held_self_avoidance: the held object against the robot's own segments in the
+        obstacle term, behind the held term.  After set_held_object_avoidance and before the first
+        update; it cannot be undone."""
+        self._check(self._L.mppi_set_held_self_avoidance(self._h))
+
+    @property
+    def held_self_avoidance(self):
+        on = C.c_int(0)
+        self._check(self._L.mppi_get_held_self_avoidance(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_held_self(self, cfg):
+        """mppi_set_held_self: replace the configuration (a HeldSelf; None: none).  Between any two
+        updates; every rank of a sharded run sets the same one."""
+        if cfg is None:
+            self._check(self._L.mppi_set_held_self(self._h, None))
+        else:
+            c = cfg.to_c()
+            self._check(self._L.mppi_set_held_self(self._h, C.byref(c)))
+
+    @property
+    def held_self(self):
+        """The current HeldSelf (mppi_get_held_self), or None with no configuration."""
+        c, on = abi.mppi_held_self(), C.c_int(0)
+        self._check(self._L.mppi_get_held_self(self._h, C.byref(c), C.byref(on)))
+        if not on.value:
+            return None
+        from .held_self import HeldSelf
+        return HeldSelf.from_c(c)
+
+    def get_optimal_held_self_cost(self):
+        """mppi_optimal_held_self_cost: the held-self term of the last update's filter() row summed over
+        its steps, undiscounted (get_optimal_obstacle_cost holds it too, beside the other three parts)."""
+        v = C.c_double(0.0)
+        self._check(self._L.mppi_optimal_held_self_cost(self._h, C.byref(v)))
+        return v.value
+
     def predicted_held_optimal(self):
         """mppi_predicted_held_optimal: where the held points go under the published plan, (H, 4, 3)
         world positions at q_k itself (not lagged); the rows of points the object does not have are NaN."""

@@ -637,6 +637,62 @@ mppi_status mppi_optimal_held_cost(mppi_handle *h, double *cost);
 mppi_status mppi_predicted_held_optimal(mppi_handle *h, double *out_Hx4x3);
 mppi_status mppi_predicted_held_rollouts(mppi_handle *h, const int64_t *rollouts, int64_t n, double *out_nxHx4x3);
 
+/* The held object against the robot's own links (mppi_set_held_self_avoidance): the one pair the held
+ * term leaves out.  A beam or a tray in the grasp sweeps the largest volume of anything on the robot, and
+ * the tower and the forearm are the nearest solid things to it; the reference's self-collision pairs are
+ * link spheres only and cannot see it.  One more part of the obstacle term, behind the held term.
+ *
+ * Held unit u = 0..6: units 0..3 are held points 0..3, units 4..6 held segments 0..2 (held segment s'
+ * joins held points s' and s' + 1).  Robot segment s = 0..7 joins robot points s and s + 1 (the nine
+ * points of the obstacle term: the eight sphere links, then the end effector), as on a capsule handle,
+ * at the same lagged configuration as the held points (q_0 for k = 0, q_{k-1} after).
+ * The configuration (mppi_held_self): units, bit i (i < 4) held point i, bit 4 + s' (s' < 3) held
+ * segment s' (MPPI_HELD_SELF_UNITS: all seven); segments, bit s (s < 8) robot segment s; radii[s], that
+ * segment's radius for this term only, finite and >= 0 - apart from mppi_capsule_config::segment_radii,
+ * so that segment 0 (pivot -> link 1, the 1.08-m tower) can be made as fat as the chassis.
+ * mppi_default_held_self: units 0x7F, segments 0x1F, every radius 0.1 - without the wrist and hand
+ * segments 5..7, which anything in the gripper touches.
+ * Clearance of held unit u and robot segment s:  v = d(a, b; c, e) - (radii[s] + r_u), d the one
+ * segment-segment distance above in capsule_term's orientation, the robot's segment first
+ * (a = p_s, b = p_{s+1}) and the other body second (c -> c + e): a held point has c = h_i, e = 0 and
+ * r_u = its radii[i]; a held segment has c = h_s', e = h_{s'+1} - h_s', each component one rounded
+ * subtraction, E = e . e rounded operation by operation, and r_u = its segment_radii[s'].  Zero-length
+ * robot segments (1 and 5) and held points are legal: every degenerate class of d occurs.
+ * The step's term is the sum of Left(limit)(v), with the avoidance configuration's barrier, over the
+ * masked held units that the current object has in order u = 0..6, per unit the masked robot segments in
+ * order s = 0..7.  The step's obstacle term becomes ((capsule term + field term) + held term) + self
+ * term, in that association.  With no object, no configuration or nothing masked the term is +0.0 and
+ * every cost keeps its bits.  A non-finite pose makes the term NaN, and so the rollout.
+ *
+ * mppi_set_held_self_avoidance selects the held-self kernels for the handle's life: after
+ * mppi_set_held_object_avoidance and before the first update (MPPI_ERR_INVALID otherwise, the message
+ * says which).  There is no environment switch.  mppi_set_held_self replaces the configuration between
+ * any two updates (NULL: none); it touches host state only, like mppi_set_held_object.
+ * MPPI_ERR_INVALID when the mode is off, units has a bit above 6, segments a bit above 7, or a radius is
+ * not finite or negative; a refused call changes nothing.  On sharded handles every rank sets the same
+ * one.  The filter() row of an update reads that update's configuration, also when it was replaced
+ * before the row ran; captured graphs see each update's configuration.
+ * mppi_get_held_self: present = 0 with no configuration (out untouched).
+ * mppi_optimal_held_self_cost: the self term of the last filter() row summed over its steps,
+ * undiscounted (0 before the first published update; MPPI_ERR_UNSUPPORTED on a handle without the mode);
+ * mppi_optimal_obstacle_cost returns capsule + field + held + self on such a handle.
+ * Added like the held symbols, without a version change: detect by symbol. */
+#define MPPI_HELD_SELF_UNITS 0x7Fu
+#define MPPI_HELD_SELF_UNIT_POINT(i) (1u << (i))
+#define MPPI_HELD_SELF_UNIT_SEGMENT(s) (1u << (4 + (s)))
+#define MPPI_HELD_SELF_SEGMENTS 8
+typedef struct mppi_held_self {
+    uint32_t units;
+    uint32_t segments;
+    double radii[MPPI_HELD_SELF_SEGMENTS];
+} mppi_held_self;
+void mppi_default_held_self(mppi_held_self *cfg);
+mppi_status mppi_set_held_self_avoidance(mppi_handle *h);
+mppi_status mppi_get_held_self_avoidance(mppi_handle *h, int *enabled);
+mppi_status mppi_set_held_self(mppi_handle *h, const mppi_held_self *cfg);
+mppi_status mppi_get_held_self(mppi_handle *h, mppi_held_self *out, int *present);
+mppi_status mppi_optimal_held_self_cost(mppi_handle *h, double *cost);
+
 /* Target tracking: TrackPoint follows a timed end-effector pose path over the horizon instead of
  * one fixed point.  The reference describes such targets (controller/trajectory.hpp) but feeds none
  * to an objective; here they are an opt-in mode of TrackPoint.  Nothing changes unless it is enabled.
@@ -990,6 +1046,12 @@ mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obsta
 mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
                                            int32_t count, double elapsed, const mppi_distance_field *field, const float *values,
                                            const mppi_held_object *object, double *cost);
+/* The held-self term (mppi_set_held_self_avoidance above) of `object` under `self` at the object's cached
+ * link positions and grasp-frame pose after its last call, with `config`'s limit (NULL: the defaults).
+ * object NULL or count = 0, or self NULL or with an empty mask: 0.  Needs kinematic link positions
+ * (MPPI_ERR_INVALID otherwise, like mppi_dynamics_capsule_cost): the robot's segments come from them. */
+mppi_status mppi_dynamics_held_self_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_held_object *object,
+                                         const mppi_held_self *self, double *cost);
 /* The target-tracking terms (mppi_set_target_tracking above) at the object's cached grasp-frame pose
  * after its last call: out2[0] = 100 pow(|p_EE - point|, 2), out2[1] = orientation_weight *
  * (3 - sum_ij Rt_ij Ree_ij) for `quaternion` (x, y, z, w; finite, norm in [0.5, 2], normalised here)

@@ -198,6 +198,31 @@ struct HeldObject {
     }
 };
 
+// The held object against the robot's own segments (mppi_set_held_self): units bit i held point i, bit
+// 4 + s held segment s; segments bit s robot segment s with radii[s].  The defaults are mppi_default_held_self's.
+struct HeldSelf {
+    uint32_t units = MPPI_HELD_SELF_UNITS;
+    uint32_t segments = 0x1Fu;
+    std::array<double, MPPI_HELD_SELF_SEGMENTS> radii{{0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1}};
+
+    mppi_held_self to_c() const
+    {
+        mppi_held_self c{};
+        c.units = units;
+        c.segments = segments;
+        for (int s = 0; s < MPPI_HELD_SELF_SEGMENTS; s++) c.radii[s] = radii[(size_t)s];
+        return c;
+    }
+    static HeldSelf from_c(const mppi_held_self &c)
+    {
+        HeldSelf h;
+        h.units = c.units;
+        h.segments = c.segments;
+        for (int s = 0; s < MPPI_HELD_SELF_SEGMENTS; s++) h.radii[(size_t)s] = c.radii[s];
+        return h;
+    }
+};
+
 class Trajectory {
 public:
     struct Rollout {
@@ -409,6 +434,44 @@ public:
     {
         double c = 0.0;
         if (mppi_optimal_held_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
+        return c;
+    }
+    // The held object against the robot's own segments (mppi_set_held_self_avoidance): after
+    // set_held_object_avoidance, before the first update; false and a message on stderr otherwise.
+    bool set_held_self_avoidance()
+    {
+        if (mppi_set_held_self_avoidance(m_h) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    bool held_self_avoidance() const
+    {
+        int on = 0;
+        return mppi_get_held_self_avoidance(m_h, &on) == MPPI_OK && on != 0;
+    }
+    // the configuration (mppi_set_held_self; nullptr: none), replaced between any two updates
+    bool set_held_self(const HeldSelf *config)
+    {
+        mppi_held_self c{};
+        if (config) c = config->to_c();
+        if (mppi_set_held_self(m_h, config ? &c : nullptr) == MPPI_OK) return true;
+        std::cerr << mppi_last_error(m_h) << std::endl;
+        return false;
+    }
+    bool set_held_self(const HeldSelf &config) { return set_held_self(&config); }
+    // the current configuration, or nothing
+    std::optional<HeldSelf> get_held_self() const
+    {
+        mppi_held_self c{};
+        int on = 0;
+        if (mppi_get_held_self(m_h, &c, &on) != MPPI_OK || !on) return std::nullopt;
+        return HeldSelf::from_c(c);
+    }
+    // the held-self term of the optimal rollout, summed over its steps (mppi_optimal_held_self_cost)
+    double get_optimal_held_self_cost()
+    {
+        double c = 0.0;
+        if (mppi_optimal_held_self_cost(m_h, &c) != MPPI_OK) throw std::runtime_error(mppi_last_error(m_h));
         return c;
     }
     // the held points' world paths at q_k (mppi_predicted_held_optimal / _rollouts): MPPI_HELD_POINTS x 3
@@ -797,6 +860,16 @@ public:
         double c = 0.0;
         const mppi_held_object o = held.to_c();
         check(mppi_dynamics_held_object_cost(object(), config, obstacles.data(), (int32_t)obstacles.size(), elapsed, field, values, &o, &c));
+        return c;
+    }
+    // the held-self term of `held` under `self` at the cached link positions and grasp pose
+    // (mppi_dynamics_held_self_cost)
+    double held_self_cost(const mppi::HeldObject &held, const mppi::HeldSelf &self, const mppi_obstacle_config *config = nullptr)
+    {
+        double c = 0.0;
+        const mppi_held_object o = held.to_c();
+        const mppi_held_self s = self.to_c();
+        check(mppi_dynamics_held_self_cost(object(), config, &o, &s, &c));
         return c;
     }
     // the target-tracking terms at the grasp frame's cached pose (mppi_dynamics_target_cost): position,

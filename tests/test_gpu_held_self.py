@@ -1,0 +1,664 @@
+"""The held object against the robot's own segments (mppi_set_held_self_avoidance) on the device against the
+Python composition of held_self_reference.py: the self term in every launch plan of the rollouts, both
+objectives, the tank, the simulated wrench, the separate cost kernel, the graph path and the two new rollout
+units, sharding, the handles it must equal bit for bit, the orientation of the distance, the device object, the
+refusals and the C++ surface.
+
+The pattern is test_gpu_held_object.py's: three updates at time 0 from test_gpu_link_positions.py's three
+states with its noise scaling, host-injected noise, helpers.py's bars.  The object, the set, the field and the
+configuration are replaced between the updates (held_object_sets.py, held_self_sets.py); the folded filter()
+row of an update is checked against the configuration of that update, which by then has been replaced.  The
+reference keeps books on every self clearance it evaluates, and each run asserts from them
+(test_held_self_cpu.check_books), on the device's own noise, that nothing sat within 1e-6 of the barrier's
+branch point, that the first update stayed on the inverse branch and the second took both, that the three
+updates saw every degenerate class of the segment distance and a general one, and that the self term moved
+every rollout's cost in the first two updates.
+"""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import assistedmanipulation_amd as am
+from assistedmanipulation_amd import abi
+
+import capsule_reference as CR
+import capsule_sets as CS
+import field_sets as FS
+import held_object_reference as HR
+import held_self_reference as SR
+import held_self_sets as SS
+import link_reference as LR
+import obstacle_reference as OR
+import obstacle_sets as OS
+import test_gpu_held_object as HELD
+import test_gpu_rollout_units as UNITS
+import wrench_reference as WR
+from launch_shapes import X, by_name, horizon
+from test_gpu_link_positions import SHAPES, _assert_bars, _hip, _noise_scale, _record, _states
+from test_gpu_obstacles import _close, _invalid, _set_env
+from test_gpu_predicted import FK_BAR
+from test_held_self_cpu import MARGIN, check_books
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _enable(dev, self_on=True):
+    dev.set_obstacle_capsules(CS.capsules())
+    dev.set_distance_field_avoidance()
+    dev.set_held_object_avoidance()
+    if self_on:
+        assert not dev.held_self_avoidance
+        dev.set_held_self_avoidance()
+        assert dev.held_self_avoidance and dev.held_self is None
+
+
+def _handle(conf, cost, wrench=None, self_on=True, config=None):
+    dyn = am.FrankaRidgebackDynamics(link_positions=True, simulated_wrench=wrench)
+    dev = am.Trajectory.create(conf, dyn, cost)
+    assert dev is not None and dev.link_positions
+    dev.set_obstacle_avoidance(config)
+    _enable(dev, self_on)
+    dev.set_noise_source(abi.MPPI_NOISE_HOST_INJECTED)
+    return dyn, dev
+
+
+def _print_books(tag, term):
+    b = term.sbooks
+    print("%s self books: least margin %.3e, least v %.4f, %s, evaluated %d, classes %s"
+          % (tag, b.least_margin, b.least_v, sorted(b.branches), b.evaluated, sorted(b.classes)))
+
+
+def _guards(term, j, tag, classes, H):
+    """The reference's book guards on this run's noise: the self term's, and for the terms beside it that no
+    clearance sat where the device and the reference may part."""
+    _print_books(tag, term)
+    check_books(term, j, tag, H)
+    assert term.least_margin >= MARGIN and term.fbooks.least_margin >= MARGIN and term.fbooks.edge >= MARGIN, (tag, j)
+    assert term.hbooks.least_margin >= MARGIN and term.hbooks.edge >= MARGIN, (tag, j)
+    classes |= term.sbooks.classes
+    if j == 2:
+        assert set(CR.DEGENERATE) <= classes and classes & set(CR.PROPER), (tag, classes)
+
+
+def _costs(comp, x, U, eps, t0=0.0):
+    """comp.costs, and per rollout the discounted sum of its self terms."""
+    J, part = np.zeros(eps.shape[0]), np.zeros(eps.shape[0])
+    for r in range(eps.shape[0]):
+        J[r] = comp.rollout(x, U + eps[r], t0)[0]
+        part[r] = sum(comp.gamma ** k * t for k, t in enumerate(comp.term.self_steps))
+    return J, part
+
+
+def _assert_moved(tag, J, part):
+    """The self term moved every rollout's cost: its discounted sum is positive and shows in the cost's bits."""
+    assert np.all(part > 0.0) and np.all(J - part != J), (tag, float(part.min()))
+
+
+def _read_outs(dev, term, ob, total, tag):
+    """The four parts of the optimal rollout's obstacle term, their sum and the total against the reference."""
+    _close(dev.get_optimal_held_self_cost(), term.self_steps.sum(), tag + " optimal held-self cost")
+    _close(dev.get_optimal_held_cost(), term.held_steps.sum(), tag + " optimal held cost")
+    _close(dev.get_optimal_field_cost(), term.field_steps.sum(), tag + " optimal field cost")
+    _close(dev.get_optimal_obstacle_cost(), ob.sum(), tag + " optimal obstacle cost")
+    _close(dev.get_optimal_total_cost(), total, tag + " optimal total")
+
+
+def _run(name, cost, monkeypatch, plans=True):
+    """test_gpu_held_object.py::_run on a held-self handle: before update j the set, the field, the object and
+    the configuration of held_self_sets are put in place."""
+    _, S, H, keep, req, sw, first, pend = by_name(name)
+    _set_env(monkeypatch, req, sw)
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    table = am.constant_forecast(H)
+    dyn, dev = _handle(conf, cost)
+    assert dev.H == H and dev.R == S + 2
+    dev.set_forecast(table)
+    comp = SR.Composition(conf, dyn.model, cost, table, capsules=CS.capsules())
+    states, scale = _states(), _noise_scale(H)
+    rng = np.random.default_rng(11)
+    sd = np.sqrt(np.diag(conf.covariance)) * scale
+    U = np.zeros((H, dev.C))
+    prev, classes = None, set()
+    for j, (x, held, field, (obstacles, t_ref), cfg) in enumerate(zip(states, SS.objects(), SS.fields(), SS.sets(), SS.configurations())):
+        tag = "%s upd %d" % (name, j)
+        dev.set_obstacles(obstacles, t_ref)
+        dev.set_distance_field(field)
+        dev.set_held_object(held)
+        dev.set_held_self(cfg)
+        assert dev.held_self == cfg and dev.held_object == held
+        comp.field, comp.held, comp.held_self = field, held, cfg
+        term = comp.set_obstacles(obstacles, t_ref)
+        dev.inject_noise(rng.standard_normal((dev.noise_draws(0.0), dev.C)) * sd)
+        dev.update(x, 0.0)
+        info = dev.update_info()
+        assert info["wait_timeouts"] == 0 and info["cooperative"] == 1, (tag, info)
+        if plans:
+            want = first if j == 0 else pend
+            assert info["folded_filter"] == want[5] and info["objective_in_launch"] == want[6], (tag, info)
+        if info["folded_filter"]:   # the previous update's filter() row: its own configuration, replaced since
+            comp.term = prev
+            ref = comp.rollout(states[j - 1], U)[0]
+            comp.term = term
+            _close(dev.debug_folded_cost(), ref, tag + " folded filter()")
+        eps = dev.noise()
+        J, moved = _costs(comp, x, U, eps)
+        w, g, Un = LR.mppi_update(conf, J, eps, U)
+        _assert_bars(tag, dev.costs(), J, dev.get_weights(), w, dev.get_optimal_rollout(), Un, H)
+        U = dev.get_optimal_rollout()
+        _guards(term, j, tag, classes, H)
+        if j < 2:
+            _assert_moved(tag, J, moved)
+        if not plans:
+            ref, _, ob = comp.rollout(x, U)
+            _read_outs(dev, term, ob, ref, tag)
+        prev = term
+    ref, sc, ob = comp.rollout(states[2], U)
+    _read_outs(dev, comp.term, ob, ref, name)
+    return dev, comp
+
+
+# ---- 1. parity against the composition, every launch plan ---------------------------------------
+
+@pytest.mark.parametrize("name", SHAPES)
+def test_update_against_the_composition(name, monkeypatch):
+    _run(name, SS.objective(), monkeypatch)
+
+
+def test_read_outs_after_every_update(monkeypatch):
+    """The optimal rollout read after each update (filter() runs by itself): the self, held, field, obstacle and
+    total costs against the reference's sums; the obstacle cost holds all four parts."""
+    dev, comp = _run("r19_h33", SS.objective(), monkeypatch, plans=False)
+    assert dev.get_optimal_obstacle_cost() > dev.get_optimal_held_self_cost() > 0.0
+
+
+# ---- 2. other objectives and modes --------------------------------------------------------------
+
+def test_track_point(monkeypatch):
+    _run("r19_h33", SS.objective("track_point"), monkeypatch)
+
+
+def test_energy_tank(monkeypatch):
+    _run("r19_h33", SS.objective(energy=True), monkeypatch)
+
+
+def test_simulated_wrench_forecast(monkeypatch):
+    """The pushed robot with the self term: test_gpu_held_object.py's wrench test on a held-self handle."""
+    from test_gpu_simulated_wrench import TIMES, _assert_update, _state
+    _, S, H, keep, req, sw, _, _ = by_name("r19_h33")
+    _set_env(monkeypatch, req, sw)
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    cost = SS.objective()
+    table = WR.forecast_table(H)
+    dyn, dev = _handle(conf, cost, wrench="forecast")
+    dev.set_forecast(table)
+    ref = SR.WrenchComposition(conf, dyn.model, cost, "forecast", table, capsules=CS.capsules())
+    sd = np.sqrt(np.diag(conf.covariance))
+    rng, shift, dt = np.random.default_rng(11), WR.Shift(), dev.get_time_step()
+    prev, classes = None, set()
+    for j, (t, held, field, (obstacles, t_ref), cfg) in enumerate(zip(TIMES, SS.objects(), SS.fields(), SS.sets(), SS.configurations())):
+        tag = "wrench upd %d" % j
+        x0 = _state(j)
+        U_prev = dev.get_optimal_rollout()
+        U_shift = WR.shifted(U_prev, shift(t, dt))
+        dev.set_obstacles(obstacles, t_ref)
+        dev.set_distance_field(field)
+        dev.set_held_object(held)
+        dev.set_held_self(cfg)
+        ref.field, ref.held, ref.held_self = field, held, cfg
+        term = ref.set_obstacles(obstacles, t_ref)
+        dev.inject_noise(rng.standard_normal((dev.noise_draws(t), 12)) * sd)
+        dev.update(x0, t)
+        info = dev.update_info()
+        assert info["wait_timeouts"] == 0, (tag, info)
+        if info["folded_filter"]:
+            ref.term = prev[0]
+            want = ref.rollout(prev[1], U_prev, prev[2])[0]
+            ref.term = term
+            _close(dev.debug_folded_cost(), want, tag + " folded filter()")
+        eps = dev.noise()
+        J, moved = _costs(ref, x0, U_shift, eps, t)
+        w, g, Un = LR.mppi_update(conf, J, eps, U_shift)
+        _assert_update(tag, dev, J, w, g, Un, H)
+        _print_books(tag, term)
+        b = term.sbooks   # (the pushed robot's states are test_gpu_simulated_wrench's: the margin and the motion hold there too)
+        assert b.evaluated > 0 and b.least_margin >= MARGIN, (tag, b.least_margin)
+        assert term.least_margin >= MARGIN and term.fbooks.least_margin >= MARGIN and term.hbooks.least_margin >= MARGIN, tag
+        if j < 2:
+            _assert_moved(tag, J, moved)
+        prev = (term, x0, t)
+    want, _, ob = ref.rollout(x0, dev.get_optimal_rollout(), TIMES[-1])
+    _close(dev.get_optimal_total_cost(), want, "wrench optimal total")
+    _close(dev.get_optimal_held_self_cost(), ref.term.self_steps.sum(), "wrench optimal held-self cost")
+
+
+# ---- 3. paths ------------------------------------------------------------------------------------
+
+def test_in_launch_objective_against_the_cost_kernel(monkeypatch):
+    """The same inputs through the launch's own objective and through fr_step_cost_hs_kernel
+    (MPPI_COSTS_IN_LAUNCH=0), r147_h64: costs and U* bit for bit."""
+    _, S, H, keep, req, sw, _, _ = by_name("r147_h64")
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    cost = SS.objective()
+    _set_env(monkeypatch, req, "")
+    a = _handle(conf, cost)[1]
+    _set_env(monkeypatch, req, "c")
+    b = _handle(conf, cost)[1]
+    rng = np.random.default_rng(4)
+    sd = np.sqrt(np.diag(conf.covariance)) * _noise_scale(H)
+    for j, (x, held, field, (obstacles, t_ref), cfg) in enumerate(zip(_states(), SS.objects(), SS.fields(), SS.sets(), SS.configurations())):
+        eps = rng.standard_normal((a.noise_draws(0.0), a.C)) * sd
+        for t in (a, b):
+            t.set_forecast(am.constant_forecast(H))
+            t.set_obstacles(obstacles, t_ref)
+            t.set_distance_field(field)
+            t.set_held_object(held)
+            t.set_held_self(cfg)
+            t.inject_noise(eps)
+            t.update(x, 0.0)
+            assert t.update_info()["wait_timeouts"] == 0
+        assert a.update_info()["objective_in_launch"] == 1 and b.update_info()["objective_in_launch"] == 0
+        np.testing.assert_array_equal(a.costs(), b.costs(), err_msg="update %d costs" % j)
+        np.testing.assert_array_equal(a.get_optimal_rollout(), b.get_optimal_rollout(), err_msg="update %d U*" % j)
+        assert a.get_optimal_held_self_cost() == b.get_optimal_held_self_cost() > 0.0
+
+
+def _philox(conf, graph=0, self_on=True, wrench=False, cost=None):
+    dyn = am.FrankaRidgebackDynamics(link_positions=True, simulated_wrench="state" if wrench else False)
+    t = am.Trajectory.create(conf, dyn, cost or am.AssistedManipulation())
+    assert t is not None
+    t.set_obstacle_avoidance()
+    _enable(t, self_on)
+    t.set_graph(graph)
+    t.set_noise_source(abi.MPPI_NOISE_DEVICE_PHILOX, seed=0x5EED)
+    t.set_forecast(am.constant_forecast(t.H))
+    return t
+
+
+def _unit_run(name, wrench, graph):
+    """test_gpu_held_object._unit_run for the held-self cell: the same objective, set, field, states, times and
+    objects (a beam, put down, a tray), with the default configuration, then the tower's, then none.
+    ([(costs, weights, optimal rollout)], graph updates, the last update's optimal held-self cost)."""
+    _, S, H, keep = by_name(name)[:4]
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    t = _philox(conf, graph, wrench=wrench, cost=OS.objective())
+    assert t.H == H and t.R == S + 2
+    f = FS.field_f()
+    t.set_distance_field(am.DistanceField(f.values, f.origin, f.voxel, mask=f.mask | am.MASK_HELD, segment_samples=f.segment_samples))
+    t.set_obstacles(HELD._held_bits(CS.set_c()), CS.T_REF_C)
+    x = am.huddled_state()
+    x[24:30] = WR.W0
+    rec = []
+    for j, (tm, held, cfg) in enumerate(zip(UNITS.TIMES, [SS.objects()[0], None, SS.objects()[1]], [am.HeldSelf(), SS.tower(), SS.wrist()])):
+        if j == 2:
+            x = x.copy()
+            x[12 + 4] = 0.3
+        t.set_held_object(held)
+        t.set_held_self(cfg)
+        t.update(x, tm)
+        assert t.update_info()["wait_timeouts"] == 0
+        rec.append((t.costs().copy(), t.get_weights().copy(), t.get_optimal_rollout().copy()))
+    # (read once, at the end: reading runs the pending filter() by itself, and an update without a folded
+    # filter() row is not a graph update)
+    return rec, t.graph_updates(), t.get_optimal_held_self_cost()
+
+
+@pytest.mark.parametrize("wrench", (0, 1))
+@pytest.mark.parametrize("name", UNITS.SHAPES)
+def test_graph_equals_eager_and_the_new_cells_differ(name, wrench, monkeypatch):
+    """What test_gpu_rollout_units.py holds the older cells to, for cells (6, 0) and (6, 1): the graph path gives
+    the eager launches' bits, with the object and the configuration replaced between the replays, and the first
+    update's costs differ from cell 5's on the same inputs (two cells with the same costs ran the same unit)."""
+    for v in UNITS.ENV:
+        monkeypatch.delenv(v, raising=False)
+    eager, eager_graphs, eager_self = _unit_run(name, wrench, 0)
+    graph, graphs, graph_self = _unit_run(name, wrench, 1)
+    pend = by_name(name)[7]
+    want = len(UNITS.TIMES) - 1 if pend[0] == X and pend[5] else 0
+    assert eager_graphs == 0 and graphs == want, (eager_graphs, graphs, want)
+    for j, (a, b) in enumerate(zip(eager, graph)):
+        for what, u, v in zip(("costs", "weights", "optimal"), a, b):
+            np.testing.assert_array_equal(u, v, err_msg="update %d %s" % (j, what))
+    assert eager_self == graph_self > 0.0      # the tray's under the wrist configuration
+    assert np.all(np.isfinite(eager[0][0]))
+    cell5 = HELD._unit_run(name, wrench, 0)[0][0][0]
+    assert cell5.shape == eager[0][0].shape and np.all(eager[0][0] != cell5), (name, wrench)
+
+
+def test_two_shards_equal_one_handle(monkeypatch):
+    """Two phase-split shards against one handle at 128 x 32, every rank with the same object and
+    configuration: test_gpu_held_object.py's structure and bars."""
+    _set_env(monkeypatch, 0, "")
+    conf = am.frankaridgeback_configuration(rollouts=128, horison=horizon(32), keep_best_rollouts=20, threads=8)
+    world = 2
+    single, shards = _philox(conf), [_philox(conf) for _ in range(world)]
+    assert single.H == 32
+    for r, sh in enumerate(shards):
+        sh.set_shard(world, r)
+    hip = _hip()
+    R, HC = single.R, single.H * single.C
+    x = am.huddled_state()
+
+    def allreduce(ptrs, n):
+        bufs = [np.zeros(n) for _ in ptrs]
+        for p, b in zip(ptrs, bufs):
+            assert hip.hipMemcpy(b.ctypes.data, p, n * 8, 2) == 0   # D2H
+        s = bufs[0].copy()
+        for b in bufs[1:]:
+            s += b
+        for p in ptrs:
+            assert hip.hipMemcpy(p, s.ctypes.data, n * 8, 1) == 0   # H2D
+
+    for j, (held, field, (obstacles, t_ref), cfg) in enumerate(zip(SS.objects(), SS.fields(), SS.sets(), SS.configurations())):
+        t = 0.05 * j
+        for h in [single] + shards:
+            h.set_obstacles(obstacles, t_ref)
+            h.set_distance_field(field)
+            h.set_held_object(held)
+            h.set_held_self(cfg)
+        single.update(x, t)
+        for sh in shards:
+            sh.update_phase1(x, t)
+        hip.hipDeviceSynchronize()
+        allreduce([sh.device_costs_ptr() for sh in shards], R + 1)   # + slot R: wait timeouts
+        for sh in shards:
+            sh.update_phase2()
+        hip.hipDeviceSynchronize()
+        allreduce([sh.device_gradient_ptr() for sh in shards], HC)
+        for sh in shards:
+            sh.update_phase3(t)
+        cu = single.costs()
+        delta = np.nanmax(cu) - np.nanmin(cu)
+        assert single.update_info()["wait_timeouts"] == 0 and single.get_optimal_held_self_cost() > 0.0
+        for sh in shards:
+            cs = sh.costs()
+            if j == 0:
+                np.testing.assert_array_equal(cs, cu)
+            assert np.all(np.abs(cs - cu) <= 1e-11 * (delta + np.abs(cu)))
+            assert np.max(np.abs(sh.get_optimal_rollout() - single.get_optimal_rollout())) <= 1e-12
+            assert np.max(np.abs(sh.get_weights() - single.get_weights())) <= 3e-15
+            assert sh.argmin() == single.argmin() and sh.update_info()["wait_timeouts"] == 0
+
+
+# ---- 4. the handles it must equal bit for bit ------------------------------------------------------
+
+def test_nothing_configured_equals_a_held_handle(monkeypatch):
+    """A held-self handle with no configuration (a), with no unit masked (c) and with no robot segment masked (d)
+    against a held handle (b), three updates with the objects, sets and fields of held_object_sets: costs,
+    weights and U* bit for bit (the term is skipped by a uniform branch on the masks).  Handle e carries the
+    wrist configuration through the first update and clears it: its first costs differ, and from the second
+    update on it gives the held handle's bits for the same inputs (one step a horizon, so the first update leaves
+    U* alone whatever it cost)."""
+    _set_env(monkeypatch, 0, "")
+    conf = am.frankaridgeback_configuration(rollouts=147, horison=horizon(20), keep_best_rollouts=20, threads=8)
+    a, b, c, d = _philox(conf), _philox(conf, self_on=False), _philox(conf), _philox(conf)
+    assert a.held_self_avoidance and not b.held_self_avoidance
+    c.set_held_self(am.HeldSelf(units=0))
+    d.set_held_self(am.HeldSelf(segments=0))
+    for j, (x, held, field, (obstacles, t_ref)) in enumerate(zip(_states(), SS.objects(), SS.fields(), SS.sets())):
+        for t in (a, b, c, d):
+            t.set_obstacles(obstacles, t_ref)
+            t.set_distance_field(field)
+            t.set_held_object(held)
+            t.update(x, 0.03 * j)
+            assert t.update_info()["wait_timeouts"] == 0
+        for t in (a, c, d):
+            for what, u, v in zip(("noise", "costs", "optimal", "weights"), _record(t), _record(b)):
+                np.testing.assert_array_equal(u, v, err_msg="update %d %s" % (j, what))
+            assert t.get_optimal_obstacle_cost() == b.get_optimal_obstacle_cost() and t.get_optimal_held_self_cost() == 0.0
+            assert t.get_optimal_held_cost() == b.get_optimal_held_cost() > 0.0
+    assert a.get_optimal_total_cost() == b.get_optimal_total_cost() == c.get_optimal_total_cost() == d.get_optimal_total_cost()
+    conf1 = am.frankaridgeback_configuration(rollouts=19, horison=horizon(1), keep_best_rollouts=5, threads=8)
+    e, f = _philox(conf1), _philox(conf1, self_on=False)
+    assert e.H == 1
+    for j, (x, field, (obstacles, t_ref)) in enumerate(zip(_states(), SS.fields(), SS.sets())):
+        for t in (e, f):
+            t.set_obstacles(obstacles, t_ref)
+            t.set_distance_field(field)
+            t.set_held_object(SS.objects()[0])
+        e.set_held_self(SS.wrist() if j == 0 else None)
+        for t in (e, f):
+            t.update(x, 0.03 * j)
+            assert t.update_info()["wait_timeouts"] == 0
+        if j == 0:
+            assert np.all(e.costs() != f.costs()) and e.get_optimal_held_self_cost() > 0.0
+            np.testing.assert_array_equal(e.get_optimal_rollout(), f.get_optimal_rollout())
+        else:
+            for u, v in zip(_record(e), _record(f)):
+                np.testing.assert_array_equal(u, v, err_msg="cleared, update %d" % j)
+            assert e.get_optimal_held_self_cost() == 0.0 and e.get_optimal_obstacle_cost() == f.get_optimal_obstacle_cost()
+
+
+# ---- 5. the device object --------------------------------------------------------------------------
+
+def _stepped(obj, x, n):
+    """The object stepped n times from x under a fixed control: the state its cached kinematics belong to.  A
+    step runs calculate() at the state it starts from and integrates afterwards (the reference's lag), so after
+    n > 0 steps the cached link positions and grasp pose are those of the state before the last step."""
+    obj.set_state(x, 0.0)
+    u = np.array([0.2, -0.1, 0.3, 0.5, -0.6, 0.4, -0.5, 0.6, -0.4, 0.5, 0.0, 0.0])
+    at = np.asarray(x, dtype=np.float64).copy()
+    for _ in range(n):
+        at = np.asarray(obj.get_state(), dtype=np.float64).copy()
+        obj.step(u, 0.05)
+    return at
+
+
+def test_robot_segment_first_held_unit_second(monkeypatch):
+    """One held point against one robot segment: the device object's held_self_cost is its capsule_cost of that
+    segment against a sphere obstacle at the held point's world position, bit for bit, with the same split of the
+    radii (the segment's radii[s], the point's r_u as the sphere's).  The object is put at stepped states, q_k of a
+    handle's predicted optimal rollout, and the handle's predicted held path says where the point is there.
+
+    That path cannot itself be the sphere's centre for a comparison of bits: predicted_held forms the pose with
+    link_fk and the rollout kernels' fsincos, the object caches its own from fk_bodies and the library's sin and
+    cos, and the two agree to test_gpu_predicted.FK_BAR, not to the bit.  Fed the path's position at step 32 the
+    costs were 2.2543705632372344 and 2.2543705632372335 (the first 32 comparisons, at steps 0 and 7, were equal).
+    The centre is therefore the object's own point, h_i = p_ee + Ree c_i from the pose it reports, formed on the
+    host operation for operation as held_points forms it; the predicted path has to agree with it to FK_BAR."""
+    _, S, H, keep, req, sw, _, _ = by_name("r19_h33")
+    _set_env(monkeypatch, req, sw)
+    conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
+    dyn, dev = _handle(conf, SS.objective())
+    dev.set_forecast(am.constant_forecast(H))
+    held = am.HeldObject([(0.05, -0.3, 0.1), (0.0, 0.3, 0.05)], (0.03, 0.035), (0.025,))
+    dev.set_held_object(held)
+    rng = np.random.default_rng(3)
+    dev.inject_noise(rng.standard_normal((dev.noise_draws(0.0), dev.C)) * np.sqrt(np.diag(conf.covariance)))
+    x0 = _states()[1]
+    dev.update(x0, 0.0)
+    pred, paths = dev.predicted_optimal(), dev.predicted_held_optimal()
+    obj = am.PinocchioDynamicsObject.create(x0, link_positions=True)
+    config = am.ObstacleAvoidance(limit=(0.01, 2.0, 1e8))
+    checked = 0
+    for k in (0, 7, H - 1):
+        x = x0.copy()
+        x[:12], x[12:24] = pred.position[k], pred.velocity[k]
+        obj.set_state(x, 0.0)
+        row = obj.get_end_effector_state_row()
+        p_ee = row[abi.MPPI_EE_POSITION:abi.MPPI_EE_POSITION + 3]
+        Ree = row[abi.MPPI_EE_ROTATION:abi.MPPI_EE_ROTATION + 9].reshape(3, 3)
+        own = np.array(HR.world_points(held, p_ee, Ree))
+        gap = np.abs(own - paths[k, :2]).max()
+        print("step %d: the object's held points and the predicted path differ by %.3e m" % (k, gap))
+        assert gap <= FK_BAR
+        for i in range(2):
+            for s in range(8):
+                radii = [0.02 * (n + 1) for n in range(8)]
+                cfg = am.HeldSelf(units=am.held_self_unit_point(i), segments=1 << s, radii=radii)
+                sphere = am.SphereObstacle(own[i], held.radii[i], mask=am.mask_segment(s))
+                got = obj.held_self_cost(config, held, cfg)
+                want = obj.capsule_cost(config, am.ObstacleCapsules(radii), [sphere], 0.0)
+                print("step %d point %d segment %d: held-self %.17g capsule %.17g" % (k, i, s, got, want))
+                assert got == want > 0.0, (k, i, s, got, want)
+                checked += 1
+    assert checked == 48
+
+
+def test_device_object_held_self_cost(monkeypatch):
+    """PinocchioDynamicsObject.held_self_cost at several stepped states against the scalar reference, 1e-12
+    relative (test_gpu_held_object.py's bar for the object): the tests' objects and configurations, every unit
+    against every segment alone, and by hand: nothing held, no configuration and empty masks are exactly 0, a NaN
+    pose is NaN; the refusals."""
+    monkeypatch.delenv("MPPI_LINK_POSITIONS", raising=False)
+    model = am.FrankaRidgebackDynamics().model
+    obj = am.PinocchioDynamicsObject.create(am.huddled_state(), link_positions=True)
+    config = am.ObstacleAvoidance(limit=(0.01, 2.0, 1e8))
+    tray = SS.objects()[1]
+    classes = set()
+    for n, x0 in zip((0, 3, 6), _states()):
+        x = _stepped(obj, x0, n)
+        q = x[:12]
+        pts, (p, R) = OR.robot_points(model, q), HR.grasp_pose(model, q)
+
+        def check(held, cfg, conf=None, what=""):
+            term = SR.Term(conf or am.ObstacleAvoidance(), am.ObstacleCapsules(), [], 0.0, None, held, cfg)
+            want = term.self_at(pts, p, R)
+            got = obj.held_self_cost(conf, held, cfg)
+            assert abs(got - want) <= 1e-12 * max(abs(want), 1.0), (what, n, got, want)
+            return term, got
+
+        for held, cfg in zip(SS.objects(), SS.configurations()):
+            term, got = check(held, cfg, None, "the tests' configurations")
+            assert got > 0.0 and term.sbooks.evaluated > 0
+            check(held, cfg, config, "the tests' configurations, another limit")
+            check(held, am.HeldSelf(), config, "the defaults")
+        for u in range(7):
+            for s in range(8):
+                cfg = am.HeldSelf(units=1 << u, segments=1 << s, radii=[0.01 * (i + 1) for i in range(8)])
+                term, got = check(tray, cfg, config, "unit %d segment %d" % (u, s))
+                assert term.sbooks.evaluated == 1 and got > 0.0
+                classes |= term.sbooks.classes
+    assert set(CR.DEGENERATE) <= classes and classes & set(CR.PROPER), classes
+    # by hand
+    beam = SS.objects()[0]
+    assert obj.held_self_cost(None, None, am.HeldSelf()) == 0.0
+    assert obj.held_self_cost(None, am.HeldObject(np.zeros((0, 3)), ()), am.HeldSelf()) == 0.0
+    assert obj.held_self_cost(None, beam, None) == 0.0
+    assert obj.held_self_cost(None, beam, am.HeldSelf(units=0)) == 0.0
+    assert obj.held_self_cost(None, beam, am.HeldSelf(segments=0)) == 0.0
+    assert obj.held_self_cost(None, SS.objects()[2], am.HeldSelf(units=0x7E)) == 0.0       # units the tip does not have
+    assert obj.held_self_cost(None, beam, am.HeldSelf()) > 0.0
+    bad = am.huddled_state()
+    bad[5] = np.nan
+    obj.set_state(bad, 0.0)
+    assert np.isnan(obj.held_self_cost(None, beam, am.HeldSelf()))
+    assert obj.held_self_cost(None, beam, am.HeldSelf(units=0)) == 0.0                      # nothing masked: +0.0 whatever the pose
+    obj.set_state(am.huddled_state(), 0.0)
+    v = C.c_double(0.0)
+    o = beam.to_c()
+    for units, segments, radius, word in ((0x80, 0x1F, 0.1, "units"), (0x7F, 0x100, 0.1, "segments"), (0x7F, 0x1F, -0.1, "radii"),
+                                          (0x7F, 0x1F, np.nan, "radii")):
+        c = am.HeldSelf().to_c()
+        c.units, c.segments, c.radii[3] = units, segments, radius
+        assert obj._L.mppi_dynamics_held_self_cost(obj._h, None, C.byref(o), C.byref(c), C.byref(v)) == abi.MPPI_ERR_INVALID
+        assert word in obj._L.mppi_last_error(None).decode()
+    stub = am.PinocchioDynamicsObject.create(am.huddled_state(), link_positions=False)
+    stub.set_state(am.huddled_state(), 0.0)
+    _invalid(lambda: stub.held_self_cost(None, beam, am.HeldSelf()), word="kinematic")
+
+
+# ---- 6. validation ---------------------------------------------------------------------------------
+
+def test_validation(monkeypatch):
+    _set_env(monkeypatch)
+    conf = am.frankaridgeback_configuration(rollouts=17, horison=0.05, keep_best_rollouts=5)
+    mk = lambda: am.Trajectory.create(conf, am.FrankaRidgebackDynamics(link_positions=True), am.AssistedManipulation())   # noqa: E731
+    wrist = SS.wrist()
+
+    # the wrong order of the enabling calls, calls on a handle without the mode, calls after the first update
+    t = mk()
+    assert not t.held_self_avoidance
+    _invalid(lambda: t.set_held_self_avoidance(), word="held object avoidance")
+    t.set_obstacle_avoidance()
+    t.set_obstacle_capsules()
+    t.set_distance_field_avoidance()
+    _invalid(lambda: t.set_held_self_avoidance(), word="held object avoidance")
+    t.set_held_object_avoidance()
+    _invalid(lambda: t.set_held_self(wrist), word="not enabled")
+    _invalid(lambda: t.set_held_self(None), word="not enabled")
+    _invalid(lambda: t.held_self, word="not enabled")
+    with pytest.raises(am.EngineError) as ei:
+        t.get_optimal_held_self_cost()
+    assert ei.value.status == abi.MPPI_ERR_UNSUPPORTED
+    t.update(am.huddled_state(), 0.0)
+    _invalid(lambda: t.set_held_self_avoidance(), word="before the first update")
+    assert not t.held_self_avoidance
+
+    f = mk()
+    f.set_obstacle_avoidance()
+    f.set_obstacle_capsules()
+    f.set_distance_field_avoidance()
+    f.set_held_object_avoidance()
+    f.set_held_self_avoidance()
+    assert f.held_self_avoidance and f.held_self is None and f.get_optimal_held_self_cost() == 0.0
+    f.set_held_self(wrist)
+    assert f.held_self == wrist
+    L, h = f._L, f._h
+
+    def refused(c, word):
+        assert L.mppi_set_held_self(h, C.byref(c)) == abi.MPPI_ERR_INVALID
+        assert word in L.mppi_last_error(h).decode(), (word, L.mppi_last_error(h).decode())
+        assert f.held_self == wrist        # a refused call changes nothing
+
+    for bit in (7, 8, 16, 31):
+        c = wrist.to_c()
+        c.units = 1 << bit
+        refused(c, "units")
+    for bit in (8, 9, 24, 31):
+        c = wrist.to_c()
+        c.segments = 1 << bit
+        refused(c, "segments")
+    for value in (-0.1, np.nan, np.inf, -np.inf):
+        for s in (0, 7):
+            c = wrist.to_c()
+            c.radii[s] = value
+            refused(c, "radii")
+    f.set_held_object(SS.objects()[0])
+    f.update(am.huddled_state(), 0.0)
+    assert f.update_info()["wait_timeouts"] == 0 and f.get_optimal_held_self_cost() > 0.0
+    assert f.get_optimal_obstacle_cost() >= f.get_optimal_held_self_cost()
+    f.set_held_self(SS.tip())        # replaced between updates, also after the first
+    assert f.held_self == SS.tip()
+    f.set_held_self(None)
+    assert f.held_self is None
+    f.update(am.huddled_state(), 0.01)
+    assert f.get_optimal_held_self_cost() == 0.0
+    f.set_held_self(am.HeldSelf())
+    f.set_held_object(None)          # a configuration and nothing held: no term
+    f.update(am.huddled_state(), 0.02)
+    assert f.get_optimal_held_self_cost() == 0.0
+    _invalid(lambda: f.set_held_self_avoidance(), word="before the first update")
+    assert f.held_self_avoidance
+
+    # a point-mass handle
+    pm = am.Trajectory.create(am.point_mass_configuration(rollouts=64, horison=0.08, keep_best_rollouts=20), am.PointMassDynamics(), am.QuadraticCost())
+    with pytest.raises(am.EngineError):
+        pm.set_held_self_avoidance()
+    assert not pm.held_self_avoidance
+    with pytest.raises(am.EngineError):
+        pm.set_held_self(wrist)
+
+
+# ---- 7. the C++ surface ----------------------------------------------------------------------------
+
+def test_cpp_held_self_surface_on_the_device(monkeypatch):
+    _set_env(monkeypatch)
+    cpp = os.path.join(REPO, "tests", "cpp")
+    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "held_self.mk"])
+    out = subprocess.check_output([os.path.join(cpp, "build", "held_self"), "gpu"], timeout=300).decode()
+    lines = [json.loads(l) for l in out.strip().split("\n")]
+    assert lines[0] == {"cpu": "ok"}
+    assert lines[1] == {"before_held": False, "config_before_avoidance": False}
+    assert lines[2]["with_wrist"] > 0.0 and lines[2]["obstacle_cost"] >= lines[2]["with_wrist"] and lines[2]["cleared"] == 0.0
+    assert lines[2]["with_defaults"] > 0.0 and lines[2]["units7"] is False and lines[2]["late_enable"] is False
+    # the object's cost: the same program's beam and configuration through the Python object
+    d = am.PinocchioDynamicsObject.create(am.huddled_state(), link_positions=True)
+    d.set_state(am.huddled_state(), 0.0)
+    cfg = am.HeldSelf(units=0x13, segments=0xE1, radii=(0.05, 0.0, 0.0, 0.0, 0.0, 0.1, 0.12, 0.01))
+    assert lines[3]["same"] and lines[3]["object_cost"] == d.held_self_cost(None, SS.objects()[0], cfg)
