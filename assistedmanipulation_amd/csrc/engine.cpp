@@ -452,14 +452,15 @@ struct mppi_handle {
     // the first update, like link_positions) and the current set with its reference time.  Each
     // update writes them with its own time behind its step constants and wrench rows (d_steps + 2 H,
     // write_obstacle_table); the hipGraph path launches that ahead of the graph, like the wrench rows.
-    bool obstacle_avoidance = false;
+    // ob_term: the highest obstacle term enabled (OB_TERM_NONE .. OB_TERM_HELD_SELF, engine_types.hpp); every
+    // term needs the one before it, so the level says which are on (has_term below) and, + 1, the link mode
+    int ob_term = OB_TERM_NONE;
     mppi_obstacle_config ob_config{};
     mppi_obstacle ob_set[MPPI_MAX_OBSTACLES] = {};
     int32_t ob_count = 0;
     double ob_time = 0.0;
     // mppi_set_obstacle_capsules: the segments' radii (the table's tail) and the capsule kernels
     // (FR_LINKS_CAPSULES), fixed once enabled like avoidance itself
-    bool obstacle_capsules = false;
     mppi_capsule_config cap_config{};
     // mppi_set_target_tracking / mppi_set_target_path (TrackPoint): the configuration (fixed once
     // enabled, before the first update) and the current path as stored - quaternions normalised and
@@ -479,7 +480,7 @@ struct mppi_handle {
     // field_cur is the grid that holds the current field.  An update's table names field_cur, so its
     // filter() row, standalone or folded into the next launch, reads its own update's grid whatever
     // was set since.
-    bool field_avoidance = false, field_present = false;
+    bool field_present = false;
     mppi_distance_field field{};
     float *d_field[2] = {nullptr, nullptr};
     size_t field_cap[2] = {0, 0};
@@ -490,11 +491,11 @@ struct mppi_handle {
     // mppi_set_held_object_avoidance: the held-object kernels (FR_LINKS_HELD), fixed once enabled.
     // mppi_set_held_object: the object the next update's table carries (held_present false: nothing is
     // held); held_update: the object the last update ran with (mppi_predicted_held_*'s absent rows)
-    bool held_avoidance = false, held_present = false;
+    bool held_present = false;
     mppi_held_object held{}, held_update{};
     // mppi_set_held_self_avoidance: the held-self kernels (FR_LINKS_HELD_SELF), fixed once enabled.
     // mppi_set_held_self: the configuration the next update's table carries (held_self_present false: none)
-    bool held_self_avoidance = false, held_self_present = false;
+    bool held_self_present = false;
     mppi_held_self held_self{};
     // mppi_set_safety_filter: with a filter set the finish kernel writes its block to d_out_stage
     // and fr_safety_filter_kernel, next on the stream, rewrites d_U and publishes the host block
@@ -643,6 +644,9 @@ struct mppi_handle {
     std::chrono::steady_clock::time_point t_start;
     double phase_time = 0;
 };
+
+// the handle's obstacle term `term` is on (mppi_handle::ob_term: it, or one that needs it, was enabled)
+static inline bool has_term(const mppi_handle *h, int term) { return h->ob_term >= term; }
 
 static mppi_status launch_filter_standalone(mppi_handle *h);
 
@@ -1294,6 +1298,31 @@ mppi_status mppi_dynamics_link_positions(mppi_dynamics *d, double *out)
     return MPPI_OK;
 }
 
+// The mppi_dynamics_*_cost functions' shared tail: one obstacle term alone (launch_fr_object_term) at the object's
+// cached pose with the caller's table, into *cost.  field (or null): its values go to a grid on the device for the
+// launch (t.field), freed on every path.
+static mppi_status obj_term_cost(mppi_dynamics *d, int term, ObstacleTable &t, const mppi_distance_field *field, const float *values,
+                                 double *cost)
+{
+    mppi_status st = obj_buffer(d, 8);
+    if (st != MPPI_OK) return st;
+    DHIP_TRY(hipSetDevice(d->device));
+    float *grid = nullptr;
+    hipError_t e = hipSuccess;
+    if (field) {
+        const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
+        DHIP_TRY(hipMalloc((void **)&grid, n * sizeof(float)));
+        fill_field(t.field, *field, grid);
+        e = hipMemcpyAsync(grid, values, n * sizeof(float), hipMemcpyHostToDevice, d->stream);
+    }
+    if (e == hipSuccess) e = launch_fr_object_term(term, d->d_obj, t, d->d_buf, d->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (grid) (void)hipFree(grid);
+    DHIP_TRY(e);
+    return MPPI_OK;
+}
+
 mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
                                         int32_t count, double elapsed, double *cost)
 {
@@ -1305,15 +1334,9 @@ mppi_status mppi_dynamics_obstacle_cost(mppi_dynamics *d, const mppi_obstacle_co
     else mppi_default_obstacle_config(&c);
     std::string why;
     if (!check_obstacle_config(c, why) || !check_obstacles(obstacles, count, elapsed, why)) return dfail(d, MPPI_ERR_INVALID, why);
-    mppi_status st = obj_buffer(d, 8);
-    if (st != MPPI_OK) return st;
     ObstacleTable t{};
     fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0);   // tau = elapsed
-    DHIP_TRY(hipSetDevice(d->device));
-    DHIP_TRY(launch_fr_object_obstacles(d->d_obj, t, d->d_buf, d->stream));
-    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    DHIP_TRY(hipStreamSynchronize(d->stream));
-    return MPPI_OK;
+    return obj_term_cost(d, OB_TERM_POINTS, t, nullptr, nullptr, cost);
 }
 
 mppi_status mppi_dynamics_target_cost(mppi_dynamics *d, const double *point3, const double *quaternion4,
@@ -1364,15 +1387,9 @@ mppi_status mppi_dynamics_capsule_cost(mppi_dynamics *d, const mppi_obstacle_con
     std::string why;
     if (!check_obstacle_config(c, why) || !check_capsule_config(cc, why) || !check_obstacles(obstacles, count, elapsed, why, true))
         return dfail(d, MPPI_ERR_INVALID, why);
-    mppi_status st = obj_buffer(d, 8);
-    if (st != MPPI_OK) return st;
     ObstacleTable t{};
     fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0, &cc);   // tau = elapsed
-    DHIP_TRY(hipSetDevice(d->device));
-    DHIP_TRY(launch_fr_object_obstacles(d->d_obj, t, d->d_buf, d->stream, true));
-    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    DHIP_TRY(hipStreamSynchronize(d->stream));
-    return MPPI_OK;
+    return obj_term_cost(d, OB_TERM_CAPSULES, t, nullptr, nullptr, cost);
 }
 
 mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obstacle_config *config,
@@ -1395,22 +1412,9 @@ mppi_status mppi_dynamics_distance_field_cost(mppi_dynamics *d, const mppi_obsta
         return MPPI_OK;
     }
     if (!check_distance_field(*field, values, why)) return dfail(d, MPPI_ERR_INVALID, why);
-    mppi_status st = obj_buffer(d, 8);
-    if (st != MPPI_OK) return st;
-    DHIP_TRY(hipSetDevice(d->device));
-    const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
-    float *grid = nullptr;
-    DHIP_TRY(hipMalloc((void **)&grid, n * sizeof(float)));
     ObstacleTable t{};
     fill_obstacle_table(t, c, nullptr, 0, 0.0, 0.0, &cc);
-    fill_field(t.field, *field, grid);
-    hipError_t e = hipMemcpyAsync(grid, values, n * sizeof(float), hipMemcpyHostToDevice, d->stream);
-    if (e == hipSuccess) e = launch_fr_object_field(d->d_obj, t, d->d_buf, d->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    (void)hipFree(grid);
-    DHIP_TRY(e);
-    return MPPI_OK;
+    return obj_term_cost(d, OB_TERM_FIELD, t, field, values, cost);
 }
 
 mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_obstacle *obstacles,
@@ -1429,26 +1433,10 @@ mppi_status mppi_dynamics_held_object_cost(mppi_dynamics *d, const mppi_obstacle
         *cost = 0.0;
         return MPPI_OK;
     }
-    mppi_status st = obj_buffer(d, 8);
-    if (st != MPPI_OK) return st;
-    DHIP_TRY(hipSetDevice(d->device));
     ObstacleTable t{};
     fill_obstacle_table(t, c, obstacles, count, elapsed, 0.0);
     fill_held(t.held, *object);
-    float *grid = nullptr;
-    hipError_t e = hipSuccess;
-    if (field) {
-        const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
-        DHIP_TRY(hipMalloc((void **)&grid, n * sizeof(float)));
-        fill_field(t.field, *field, grid);
-        e = hipMemcpyAsync(grid, values, n * sizeof(float), hipMemcpyHostToDevice, d->stream);
-    }
-    if (e == hipSuccess) e = launch_fr_object_held(d->d_obj, t, d->d_buf, d->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (grid) (void)hipFree(grid);
-    DHIP_TRY(e);
-    return MPPI_OK;
+    return obj_term_cost(d, OB_TERM_HELD, t, field, values, cost);
 }
 
 mppi_status mppi_dynamics_held_self_cost(mppi_dynamics *d, const mppi_obstacle_config *config, const mppi_held_object *object,
@@ -1468,17 +1456,11 @@ mppi_status mppi_dynamics_held_self_cost(mppi_dynamics *d, const mppi_obstacle_c
         *cost = 0.0;
         return MPPI_OK;
     }
-    mppi_status st = obj_buffer(d, 8);
-    if (st != MPPI_OK) return st;
-    DHIP_TRY(hipSetDevice(d->device));
     ObstacleTable t{};
     fill_obstacle_table(t, c, nullptr, 0, 0.0, 0.0);
     fill_held(t.held, *object);
     fill_held_self(t.self, *self);
-    DHIP_TRY(launch_fr_object_held_self(d->d_obj, t, d->d_buf, d->stream));
-    DHIP_TRY(hipMemcpyAsync(cost, d->d_buf, sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    DHIP_TRY(hipStreamSynchronize(d->stream));
-    return MPPI_OK;
+    return obj_term_cost(d, OB_TERM_HELD_SELF, t, nullptr, nullptr, cost);
 }
 
 mppi_status mppi_dynamics_safety_filter(mppi_dynamics *d, const mppi_safety_filter_desc *filter, const double *control12, double dt,
@@ -2236,10 +2218,7 @@ static FrCostArgs cost_args(const mppi_handle *h, const FrRolloutArgs &a, bool c
 // FrRolloutArgs::link_positions of the handle's launches
 static int launch_link_mode(const mppi_handle *h)
 {
-    if (h->obstacle_avoidance && h->held_avoidance && h->held_self_avoidance) return FR_LINKS_HELD_SELF;
-    if (h->obstacle_avoidance && h->held_avoidance) return FR_LINKS_HELD;
-    if (h->obstacle_avoidance && h->field_avoidance) return FR_LINKS_FIELD;
-    if (h->obstacle_avoidance) return h->obstacle_capsules ? FR_LINKS_CAPSULES : FR_LINKS_OBSTACLES;
+    if (h->ob_term != OB_TERM_NONE) return h->ob_term + 1;   // (kernels.hpp: a link mode past the kinematic one is its term + 1)
     return h->link_positions == MPPI_LINK_POSITIONS_KINEMATIC ? FR_LINKS_KINEMATIC : FR_LINKS_ZERO;
 }
 
@@ -2340,17 +2319,17 @@ static mppi_status write_obstacle_table(mppi_handle *h, double time)
 {
     h->d_steps = h->d_steps_buf[(h->update_count + 1) & 1];
     ObstacleTable t{};
-    fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time, h->obstacle_capsules ? &h->cap_config : nullptr);
-    if (h->field_avoidance) {   // the current field's grid: the next set leaves it alone
+    fill_obstacle_table(t, h->ob_config, h->ob_set, h->ob_count, time, h->ob_time, has_term(h, OB_TERM_CAPSULES) ? &h->cap_config : nullptr);
+    if (has_term(h, OB_TERM_FIELD)) {   // the current field's grid: the next set leaves it alone
         if (h->field_present) fill_field(t.field, h->field, h->d_field[h->field_cur]);
         h->field_last = h->field_present ? h->field_cur : -1;
     }
-    if (h->held_avoidance) {   // the object as it stands: this update's, whatever is set later
+    if (has_term(h, OB_TERM_HELD)) {   // the object as it stands: this update's, whatever is set later
         h->held_update = h->held_present ? h->held : mppi_held_object{};
         fill_held(t.held, h->held_update);
     }
     // (likewise the held-self configuration; none: the zeros the table starts with, nothing masked)
-    if (h->held_self_avoidance && h->held_self_present) fill_held_self(t.self, h->held_self);
+    if (has_term(h, OB_TERM_HELD_SELF) && h->held_self_present) fill_held_self(t.self, h->held_self);
     HIP_TRY(launch_obstacle_table(t, reinterpret_cast<ObstacleTable *>(h->d_steps + 2 * h->H), h->stream));
     return MPPI_OK;
 }
@@ -2401,7 +2380,7 @@ mppi_status mppi_update_phase1(mppi_handle *h, const double *state, double time)
         mppi_status st = write_wrench_rows(h, state, time);
         if (st != MPPI_OK) return st;
     }
-    if (h->obstacle_avoidance && !h->wrench_ahead) {
+    if (has_term(h, OB_TERM_POINTS) && !h->wrench_ahead) {
         mppi_status st = write_obstacle_table(h, time);
         if (st != MPPI_OK) return st;
     }
@@ -2996,7 +2975,7 @@ static mppi_status update_graph(mppi_handle *h, const double *state, double time
     // likewise the obstacle table: the current set and this update's time on every replay.  (Should
     // the capture below fail, update_eager writes the same table into the same buffer once more: one
     // redundant small launch on a path that runs at most once per handle.)
-    if (h->obstacle_avoidance) {
+    if (has_term(h, OB_TERM_POINTS)) {
         mppi_status ws = write_obstacle_table(h, time);
         if (ws != MPPI_OK) return ws;
     }
@@ -3111,7 +3090,7 @@ mppi_status mppi_set_link_positions(mppi_handle *h, int mode)
         return fail(h, MPPI_ERR_INVALID, "link-position model must be MPPI_LINK_POSITIONS_ZERO or MPPI_LINK_POSITIONS_KINEMATIC");
     // the rollout launches' kernels are part of the launch plan and of a captured graph
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "the link-position model is set before the first update");
-    if (h->obstacle_avoidance && mode != MPPI_LINK_POSITIONS_KINEMATIC)
+    if (has_term(h, OB_TERM_POINTS) && mode != MPPI_LINK_POSITIONS_KINEMATIC)
         return fail(h, MPPI_ERR_INVALID, "obstacle avoidance is enabled: the link-position model stays MPPI_LINK_POSITIONS_KINEMATIC");
     if (h->target_tracking && h->tt_config.track_orientation && mode != MPPI_LINK_POSITIONS_KINEMATIC)
         return fail(h, MPPI_ERR_INVALID, "orientation tracking is enabled: the link-position model stays MPPI_LINK_POSITIONS_KINEMATIC");
@@ -3247,24 +3226,24 @@ mppi_status mppi_set_obstacle_avoidance(mppi_handle *h, const mppi_obstacle_conf
     std::string why;
     if (!check_obstacle_config(c, why)) return fail(h, MPPI_ERR_INVALID, why);
     h->ob_config = c;
-    h->obstacle_avoidance = true;
+    h->ob_term = std::max(h->ob_term, OB_TERM_POINTS);   // (again on a capsule handle: capsules stay on)
     return MPPI_OK;
 }
 
 mppi_status mppi_get_obstacle_avoidance(mppi_handle *h, int *enabled, mppi_obstacle_config *out)
 {
     if (!h || !enabled) return MPPI_ERR_INVALID;
-    *enabled = h->obstacle_avoidance ? 1 : 0;
-    if (h->obstacle_avoidance && out) *out = h->ob_config;
+    *enabled = has_term(h, OB_TERM_POINTS) ? 1 : 0;
+    if (has_term(h, OB_TERM_POINTS) && out) *out = h->ob_config;
     return MPPI_OK;
 }
 
 mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, int32_t count, double time)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
+    if (!has_term(h, OB_TERM_POINTS)) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
     std::string why;
-    if (!check_obstacles(obstacles, count, time, why, h->obstacle_capsules, h->held_avoidance)) return fail(h, MPPI_ERR_INVALID, why);
+    if (!check_obstacles(obstacles, count, time, why, has_term(h, OB_TERM_CAPSULES), has_term(h, OB_TERM_HELD))) return fail(h, MPPI_ERR_INVALID, why);
     for (int32_t o = 0; o < count; o++) h->ob_set[o] = obstacles[o];
     h->ob_count = count;
     h->ob_time = time;
@@ -3274,7 +3253,7 @@ mppi_status mppi_set_obstacles(mppi_handle *h, const mppi_obstacle *obstacles, i
 mppi_status mppi_get_obstacles(mppi_handle *h, mppi_obstacle *out16, int32_t *count, double *time)
 {
     if (!h || !count) return MPPI_ERR_INVALID;
-    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
+    if (!has_term(h, OB_TERM_POINTS)) return fail(h, MPPI_ERR_INVALID, "obstacles: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
     *count = h->ob_count;
     if (time) *time = h->ob_time;
     if (out16)
@@ -3291,7 +3270,7 @@ void mppi_default_capsule_config(mppi_capsule_config *out)
 mppi_status mppi_set_obstacle_capsules(mppi_handle *h, const mppi_capsule_config *config)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->obstacle_avoidance)
+    if (!has_term(h, OB_TERM_POINTS))
         return fail(h, MPPI_ERR_INVALID, "obstacle capsules: obstacle avoidance is not enabled (mppi_set_obstacle_avoidance)");
     // the capsule kernels are part of the launch plan and of a captured graph, like the obstacle kernels
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "obstacle capsules are enabled before the first update");
@@ -3301,47 +3280,47 @@ mppi_status mppi_set_obstacle_capsules(mppi_handle *h, const mppi_capsule_config
     std::string why;
     if (!check_capsule_config(c, why)) return fail(h, MPPI_ERR_INVALID, why);
     h->cap_config = c;
-    h->obstacle_capsules = true;
+    h->ob_term = std::max(h->ob_term, OB_TERM_CAPSULES);
     return MPPI_OK;
 }
 
 mppi_status mppi_get_obstacle_capsules(mppi_handle *h, int *enabled, mppi_capsule_config *out)
 {
     if (!h || !enabled) return MPPI_ERR_INVALID;
-    *enabled = h->obstacle_capsules ? 1 : 0;
-    if (h->obstacle_capsules && out) *out = h->cap_config;
+    *enabled = has_term(h, OB_TERM_CAPSULES) ? 1 : 0;
+    if (has_term(h, OB_TERM_CAPSULES) && out) *out = h->cap_config;
     return MPPI_OK;
 }
 
 mppi_status mppi_set_distance_field_avoidance(mppi_handle *h)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->obstacle_capsules)
+    if (!has_term(h, OB_TERM_CAPSULES))
         return fail(h, MPPI_ERR_INVALID, "distance field avoidance: obstacle capsules are not enabled (mppi_set_obstacle_capsules)");
     // the field kernels are part of the launch plan and of a captured graph, like the capsule kernels
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "distance field avoidance is enabled before the first update");
-    h->field_avoidance = true;
+    h->ob_term = std::max(h->ob_term, OB_TERM_FIELD);
     return MPPI_OK;
 }
 
 mppi_status mppi_get_distance_field_avoidance(mppi_handle *h, int *enabled)
 {
     if (!h || !enabled) return MPPI_ERR_INVALID;
-    *enabled = h->field_avoidance ? 1 : 0;
+    *enabled = has_term(h, OB_TERM_FIELD) ? 1 : 0;
     return MPPI_OK;
 }
 
 mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *field, const float *values)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->field_avoidance)
+    if (!has_term(h, OB_TERM_FIELD))
         return fail(h, MPPI_ERR_INVALID, "distance field: field avoidance is not enabled (mppi_set_distance_field_avoidance)");
     if (!field) {   // no field from the next update on; the grids stay for the tables that name them
         h->field_present = false;
         return MPPI_OK;
     }
     std::string why;
-    if (!check_distance_field(*field, values, why, h->held_avoidance)) return fail(h, MPPI_ERR_INVALID, why);
+    if (!check_distance_field(*field, values, why, has_term(h, OB_TERM_HELD))) return fail(h, MPPI_ERR_INVALID, why);
     HIP_TRY(hipSetDevice(h->device));
     const size_t n = (size_t)field->dims[0] * (size_t)field->dims[1] * (size_t)field->dims[2];
     // the grid the last update's table does not reference: that update's filter() row may not have run
@@ -3378,7 +3357,7 @@ mppi_status mppi_set_distance_field(mppi_handle *h, const mppi_distance_field *f
 mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, int *present)
 {
     if (!h || !present) return MPPI_ERR_INVALID;
-    if (!h->field_avoidance)
+    if (!has_term(h, OB_TERM_FIELD))
         return fail(h, MPPI_ERR_INVALID, "distance field: field avoidance is not enabled (mppi_set_distance_field_avoidance)");
     *present = h->field_present ? 1 : 0;
     if (h->field_present && out) *out = h->field;
@@ -3388,25 +3367,25 @@ mppi_status mppi_get_distance_field(mppi_handle *h, mppi_distance_field *out, in
 mppi_status mppi_set_held_object_avoidance(mppi_handle *h)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->field_avoidance)
+    if (!has_term(h, OB_TERM_FIELD))
         return fail(h, MPPI_ERR_INVALID, "held object avoidance: distance field avoidance is not enabled (mppi_set_distance_field_avoidance)");
     // the held-object kernels are part of the launch plan and of a captured graph, like the field kernels
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "held object avoidance is enabled before the first update");
-    h->held_avoidance = true;
+    h->ob_term = std::max(h->ob_term, OB_TERM_HELD);
     return MPPI_OK;
 }
 
 mppi_status mppi_get_held_object_avoidance(mppi_handle *h, int *enabled)
 {
     if (!h || !enabled) return MPPI_ERR_INVALID;
-    *enabled = h->held_avoidance ? 1 : 0;
+    *enabled = has_term(h, OB_TERM_HELD) ? 1 : 0;
     return MPPI_OK;
 }
 
 mppi_status mppi_set_held_object(mppi_handle *h, const mppi_held_object *object)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->held_avoidance)
+    if (!has_term(h, OB_TERM_HELD))
         return fail(h, MPPI_ERR_INVALID, "held object: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     if (!object) {   // put down: nothing is held from the next update on
         h->held_present = false;
@@ -3423,7 +3402,7 @@ mppi_status mppi_set_held_object(mppi_handle *h, const mppi_held_object *object)
 mppi_status mppi_get_held_object(mppi_handle *h, mppi_held_object *out, int *present)
 {
     if (!h || !present) return MPPI_ERR_INVALID;
-    if (!h->held_avoidance)
+    if (!has_term(h, OB_TERM_HELD))
         return fail(h, MPPI_ERR_INVALID, "held object: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     *present = h->held_present ? 1 : 0;
     if (h->held_present && out) *out = h->held;
@@ -3441,25 +3420,25 @@ void mppi_default_held_self(mppi_held_self *cfg)
 mppi_status mppi_set_held_self_avoidance(mppi_handle *h)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->held_avoidance)
+    if (!has_term(h, OB_TERM_HELD))
         return fail(h, MPPI_ERR_INVALID, "held self avoidance: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     // the held-self kernels are part of the launch plan and of a captured graph, like the held kernels
     if (h->updated_once) return fail(h, MPPI_ERR_INVALID, "held self avoidance is enabled before the first update");
-    h->held_self_avoidance = true;
+    h->ob_term = std::max(h->ob_term, OB_TERM_HELD_SELF);
     return MPPI_OK;
 }
 
 mppi_status mppi_get_held_self_avoidance(mppi_handle *h, int *enabled)
 {
     if (!h || !enabled) return MPPI_ERR_INVALID;
-    *enabled = h->held_self_avoidance ? 1 : 0;
+    *enabled = has_term(h, OB_TERM_HELD_SELF) ? 1 : 0;
     return MPPI_OK;
 }
 
 mppi_status mppi_set_held_self(mppi_handle *h, const mppi_held_self *cfg)
 {
     if (!h) return MPPI_ERR_INVALID;
-    if (!h->held_self_avoidance)
+    if (!has_term(h, OB_TERM_HELD_SELF))
         return fail(h, MPPI_ERR_INVALID, "held self: held self avoidance is not enabled (mppi_set_held_self_avoidance)");
     if (!cfg) {   // cleared: nothing is tested from the next update on
         h->held_self_present = false;
@@ -3476,7 +3455,7 @@ mppi_status mppi_set_held_self(mppi_handle *h, const mppi_held_self *cfg)
 mppi_status mppi_get_held_self(mppi_handle *h, mppi_held_self *out, int *present)
 {
     if (!h || !present) return MPPI_ERR_INVALID;
-    if (!h->held_self_avoidance)
+    if (!has_term(h, OB_TERM_HELD_SELF))
         return fail(h, MPPI_ERR_INVALID, "held self: held self avoidance is not enabled (mppi_set_held_self_avoidance)");
     *present = h->held_self_present ? 1 : 0;
     if (h->held_self_present && out) *out = h->held_self;
@@ -3763,34 +3742,36 @@ mppi_status mppi_optimal_terms(mppi_handle *h, double *terms7)
     return MPPI_OK;
 }
 
-mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
+// The optimal rollout's obstacle terms first .. last alone (launch_fr_term_total), summed in that order,
+// ((first + ...) + last): 0 before the first update that published, else once the filter() row's records are
+// complete, from the row's own update's table behind opt_steps - and through it that update's set, grid,
+// held object and held-self configuration.  need: the term the handle must have enabled, else `off`.
+static mppi_status optimal_term_cost(mppi_handle *h, int need, const char *off, int first, int last, double *cost)
 {
     if (!h || !cost) return MPPI_ERR_INVALID;
-    if (!h->obstacle_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "obstacle cost: obstacle avoidance is not enabled");
+    if (!has_term(h, need)) return fail(h, MPPI_ERR_UNSUPPORTED, off);
     HIP_TRY(hipSetDevice(h->device));
     *cost = 0.0;
     if (!h->published_once) return MPPI_OK;   // no filter() row yet
     mppi_status st = wait_optimal(h);   // the filter() row's records are then complete
     if (st != MPPI_OK) return st;
-    // (the row's own update's table: behind opt_steps)
-    HIP_TRY(launch_fr_obstacle_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
-                                     h->stream_opt, h->obstacle_capsules));
-    if (h->field_avoidance)   // a field handle: the capsule term plus the field term
-        HIP_TRY(launch_fr_field_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 1,
-                                      h->stream_opt));
-    if (h->held_avoidance)   // a held handle: (capsule + field) + held
-        HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 2,
-                                     h->stream_opt));
-    if (h->held_self_avoidance)   // a held-self handle: ((capsule + field) + held) + self
-        HIP_TRY(launch_fr_held_self_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms + 3,
-                                          h->stream_opt));
-    const int parts = h->held_self_avoidance ? 4 : (h->held_avoidance ? 3 : (h->field_avoidance ? 2 : 1));
+    const int parts = last - first + 1;
+    for (int i = 0; i < parts; i++)
+        HIP_TRY(launch_fr_term_total(first + i, h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt,
+                                     h->d_terms + i, h->stream_opt));
     HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, parts * sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
     HIP_TRY(hipStreamSynchronize(h->stream_opt));
-    *cost = h->field_avoidance ? h->h_opt[1] + h->h_opt[2] : h->h_opt[1];
-    if (h->held_avoidance) *cost += h->h_opt[3];
-    if (h->held_self_avoidance) *cost += h->h_opt[4];
+    *cost = h->h_opt[1];
+    for (int i = 1; i < parts; i++) *cost += h->h_opt[1 + i];
     return MPPI_OK;
+}
+
+// the whole obstacle term: the point term, or ((capsule + field) + held) + self as far as the handle has them
+mppi_status mppi_optimal_obstacle_cost(mppi_handle *h, double *cost)
+{
+    if (!h) return MPPI_ERR_INVALID;
+    const int first = h->ob_term > OB_TERM_POINTS ? OB_TERM_CAPSULES : OB_TERM_POINTS;   // the capsule term stands for the point term
+    return optimal_term_cost(h, OB_TERM_POINTS, "obstacle cost: obstacle avoidance is not enabled", first, std::max(first, h->ob_term), cost);
 }
 
 void mppi_default_target_tracking_config(mppi_target_tracking_config *out)
@@ -3916,56 +3897,18 @@ mppi_status mppi_optimal_target_cost(mppi_handle *h, double *out2)
 
 mppi_status mppi_optimal_field_cost(mppi_handle *h, double *cost)
 {
-    if (!h || !cost) return MPPI_ERR_INVALID;
-    if (!h->field_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "field cost: distance field avoidance is not enabled");
-    HIP_TRY(hipSetDevice(h->device));
-    *cost = 0.0;
-    if (!h->published_once) return MPPI_OK;   // no filter() row yet
-    mppi_status st = wait_optimal(h);
-    if (st != MPPI_OK) return st;
-    // (the row's own update's table, and through it that update's grid)
-    HIP_TRY(launch_fr_field_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
-                                  h->stream_opt));
-    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
-    HIP_TRY(hipStreamSynchronize(h->stream_opt));
-    *cost = h->h_opt[1];
-    return MPPI_OK;
+    return optimal_term_cost(h, OB_TERM_FIELD, "field cost: distance field avoidance is not enabled", OB_TERM_FIELD, OB_TERM_FIELD, cost);
 }
 
 mppi_status mppi_optimal_held_cost(mppi_handle *h, double *cost)
 {
-    if (!h || !cost) return MPPI_ERR_INVALID;
-    if (!h->held_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "held cost: held object avoidance is not enabled");
-    HIP_TRY(hipSetDevice(h->device));
-    *cost = 0.0;
-    if (!h->published_once) return MPPI_OK;   // no filter() row yet
-    mppi_status st = wait_optimal(h);
-    if (st != MPPI_OK) return st;
-    // (the row's own update's table, and through it that update's object and grid)
-    HIP_TRY(launch_fr_held_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
-                                 h->stream_opt));
-    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
-    HIP_TRY(hipStreamSynchronize(h->stream_opt));
-    *cost = h->h_opt[1];
-    return MPPI_OK;
+    return optimal_term_cost(h, OB_TERM_HELD, "held cost: held object avoidance is not enabled", OB_TERM_HELD, OB_TERM_HELD, cost);
 }
 
 mppi_status mppi_optimal_held_self_cost(mppi_handle *h, double *cost)
 {
-    if (!h || !cost) return MPPI_ERR_INVALID;
-    if (!h->held_self_avoidance) return fail(h, MPPI_ERR_UNSUPPORTED, "held self cost: held self avoidance is not enabled");
-    HIP_TRY(hipSetDevice(h->device));
-    *cost = 0.0;
-    if (!h->published_once) return MPPI_OK;   // no filter() row yet
-    mppi_status st = wait_optimal(h);
-    if (st != MPPI_OK) return st;
-    // (the row's own update's table, and through it that update's object and configuration)
-    HIP_TRY(launch_fr_held_self_total(h->opt_steps, h->d_rec_opt, (int)h->H, h->opt_rec_compact, h->d_model, h->dt, h->d_terms,
-                                      h->stream_opt));
-    HIP_TRY(hipMemcpyAsync(h->h_opt + 1, h->d_terms, sizeof(double), hipMemcpyDeviceToHost, h->stream_opt));
-    HIP_TRY(hipStreamSynchronize(h->stream_opt));
-    *cost = h->h_opt[1];
-    return MPPI_OK;
+    return optimal_term_cost(h, OB_TERM_HELD_SELF, "held self cost: held self avoidance is not enabled", OB_TERM_HELD_SELF,
+                             OB_TERM_HELD_SELF, cost);
 }
 
 // Predicted trajectories (fr_predict.hip): `rows` (host) address n rollouts' records in `rec`; the
@@ -4004,7 +3947,7 @@ static mppi_status predicted_optimal(mppi_handle *h, double *out, bool held)
     if (!h || !out) return MPPI_ERR_INVALID;
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
-    if (held && !h->held_avoidance)
+    if (held && !has_term(h, OB_TERM_HELD))
         return fail(h, MPPI_ERR_INVALID, "predicted held paths: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     if (!h->published_once) return fail(h, MPPI_ERR_INVALID, "predicted optimal rollout: no update has published yet");
     HIP_TRY(hipSetDevice(h->device));
@@ -4035,7 +3978,7 @@ static mppi_status predicted_rollouts(mppi_handle *h, const int64_t *rollouts, i
     if (!h || n < 0 || (n > 0 && (!rollouts || !out))) return MPPI_ERR_INVALID;
     if (h->dyn_kind != MPPI_DYNAMICS_FRANKARIDGEBACK)
         return fail(h, MPPI_ERR_UNSUPPORTED, "predicted trajectories: FrankaRidgeback handles only");
-    if (held && !h->held_avoidance)
+    if (held && !has_term(h, OB_TERM_HELD))
         return fail(h, MPPI_ERR_INVALID, "predicted held paths: held object avoidance is not enabled (mppi_set_held_object_avoidance)");
     if (!h->updated_once) return fail(h, MPPI_ERR_INVALID, "predicted rollouts: no update has run yet");
     if (h->info[MPPI_INFO_WAIT_TIMEOUTS] != 0)

@@ -75,9 +75,6 @@ using mppi_dev::smin;
 
 // the unit's cell, and what follows from it: the link-position objective, and its obstacle term
 static_assert(FR_UNIT_LINKS >= FR_LINKS_ZERO && FR_UNIT_LINKS <= FR_LINKS_HELD_SELF && (FR_UNIT_WR == 0 || FR_UNIT_WR == 1), "no such unit");
-static_assert(OB_TERM_NONE == 0 && FR_LINKS_OBSTACLES - 1 == OB_TERM_POINTS && FR_LINKS_CAPSULES - 1 == OB_TERM_CAPSULES &&
-                  FR_LINKS_FIELD - 1 == OB_TERM_FIELD && FR_LINKS_HELD - 1 == OB_TERM_HELD &&
-                  FR_LINKS_HELD_SELF - 1 == OB_TERM_HELD_SELF, "a link mode past the kinematic one is its obstacle term + 1");
 constexpr bool UNIT_LP = FR_UNIT_LINKS != FR_LINKS_ZERO, UNIT_WR = FR_UNIT_WR != 0;
 constexpr int UNIT_OB = FR_UNIT_LINKS > FR_LINKS_KINEMATIC ? FR_UNIT_LINKS - 1 : OB_TERM_NONE;
 

@@ -35,66 +35,28 @@ using namespace mppi_cost;
 // lanes: every byte of the rollout's records is used once, through L2).  Staging through LDS took
 // 21.5 KB per wave and held a CU to seven waves, too few to hide the loads; without it the kernel
 // is bounded by registers (four waves per SIMD).
-// LP: the kinematic link-position model (FrCostArgs::link_positions): the self-collision term from
-// each record's link positions (fr_cost_terms.hpp record_self_collision)
-// (a kernel of its own, fr_step_cost_lp_kernel, from the same text: the default mode's keep their names and instructions)
+// The kinematic link-position model and the obstacle terms behind it are kernels of their own,
+// fr_step_cost_links_kernel below, from the same text: the default mode's keep their names and instructions.
 template <int CK, bool EN, bool KC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void fr_step_cost_kernel(FrCostArgs a)
 {
     constexpr bool LP = false, OB = false;
 #include "fr_step_cost_kernel_body.inc"
 }
+// LP: the kinematic link-position model (FrCostArgs::link_positions != FR_LINKS_ZERO): the self-collision term
+// from each record's link positions (fr_cost_terms.hpp record_self_collision), and behind it the obstacle
+// term OB = link mode - 1 (fr_cost_terms.hpp obstacle_cost): OB_TERM_NONE (FR_LINKS_KINEMATIC), OB_TERM_POINTS
+// (FR_LINKS_OBSTACLES: obstacle_term), OB_TERM_CAPSULES (FR_LINKS_CAPSULES: capsule_term), OB_TERM_FIELD
+// (FR_LINKS_FIELD: field_term behind it), OB_TERM_HELD (FR_LINKS_HELD: held_term behind those) or
+// OB_TERM_HELD_SELF (FR_LINKS_HELD_SELF: held_self_term behind those).
 // Two waves per SIMD here: the link positions and the pose are live beside the barrier chains, and
 // at four waves (128 VGPRs) this kernel spilled 84-164 of them; 0.223 against 0.300 ms/update at
 // 4096 x 64 with MPPI_COSTS_IN_LAUNCH=0 (profiles/link_positions/bench_costkernel_*).
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_lp_kernel(FrCostArgs a)
+template <int CK, bool EN, bool KC, int OB>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_links_kernel(FrCostArgs a)
 {
-    constexpr bool LP = true, OB = false;
-#include "fr_step_cost_kernel_body.inc"
-}
-// The same with the obstacle term (FrCostArgs::link_positions == FR_LINKS_OBSTACLES)
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_ob_kernel(FrCostArgs a)
-{
-    constexpr bool LP = true, OB = true;
-#include "fr_step_cost_kernel_body.inc"
-}
-
-// The same with segments and capsule obstacles (FR_LINKS_CAPSULES: fr_cost_terms.hpp capsule_term)
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_cap_kernel(FrCostArgs a)
-{
+    static_assert(OB >= OB_TERM_NONE && OB <= OB_TERM_HELD_SELF, "no such obstacle term");
     constexpr bool LP = true;
-    constexpr int OB = OB_TERM_CAPSULES;
-#include "fr_step_cost_kernel_body.inc"
-}
-
-// The same with the distance field behind the capsule term (FR_LINKS_FIELD: fr_cost_terms.hpp field_term)
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_df_kernel(FrCostArgs a)
-{
-    constexpr bool LP = true;
-    constexpr int OB = OB_TERM_FIELD;
-#include "fr_step_cost_kernel_body.inc"
-}
-
-// The same with a held object behind the field term (FR_LINKS_HELD: fr_cost_terms.hpp held_term)
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_ho_kernel(FrCostArgs a)
-{
-    constexpr bool LP = true;
-    constexpr int OB = OB_TERM_HELD;
-#include "fr_step_cost_kernel_body.inc"
-}
-
-// The same with the held object against the robot's own segments behind the held term (FR_LINKS_HELD_SELF:
-// fr_cost_terms.hpp held_self_term)
-template <int CK, bool EN, bool KC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fr_step_cost_hs_kernel(FrCostArgs a)
-{
-    constexpr bool LP = true;
-    constexpr int OB = OB_TERM_HELD_SELF;
 #include "fr_step_cost_kernel_body.inc"
 }
 
@@ -107,13 +69,18 @@ __global__ __launch_bounds__(64) void obstacle_table_kernel(ObstacleTable t, Obs
     for (int i = threadIdx.x; i < (int)(sizeof(ObstacleTable) / sizeof(double)); i += 64) dst[i] = src[i];
 }
 
-// The obstacle term of the filter() row summed over its steps in step order, undiscounted, as
-// fr_terms_kernel sums the reference's seven (one wave, lane = step)
-// CAP: the capsule term (fr_capsule_total_kernel)
-template <bool CAP>
-__device__ __forceinline__ void obstacle_total(const StepConst *steps, const double *rec, int H, int compact,
-                                               const DevModel *model, double dt, double *out1)
+// One obstacle term of the filter() row alone, summed over its steps in step order, undiscounted, as
+// fr_terms_kernel sums the reference's seven (one wave, lane = step), from the table of the row's own
+// update - and so that update's set, grid, held object and held-self configuration.  TERM: OB_TERM_POINTS
+// obstacle_term, OB_TERM_CAPSULES capsule_term, OB_TERM_FIELD field_term, OB_TERM_HELD held_term,
+// OB_TERM_HELD_SELF held_self_term_at - each term by itself, not the sum up to it.
+// (One wave a launch: the held-self term's link and held coordinates stay in registers through the pair
+// loop, 256 VGPRs; bounded to its twin's three waves a SIMD it spills 592 bytes a lane.)
+template <int TERM>
+__global__ __launch_bounds__(64) void fr_term_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
+                                                           const DevModel *model, double dt, double *out1)
 {
+    static_assert(TERM >= OB_TERM_POINTS && TERM <= OB_TERM_HELD_SELF, "no such obstacle term");
     const int lane = threadIdx.x;
     const ObstacleTableK T = obstacle_table_of(steps, H);
     double tot = 0.0;
@@ -122,87 +89,19 @@ __device__ __forceinline__ void obstacle_total(const StepConst *steps, const dou
         const int k = base + (lane < n ? lane : 0);
         const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);   // (q, qd) pairs and the EE position: both layouts
         double qj[10], lp[SC_LINKS][3];
+        double R9[TERM >= OB_TERM_HELD ? 9 : 1];   // body 9's rotation with the positions: the held object turns with the grasp
         for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
-        link_fk(*model, qj, lp);
+        if constexpr (TERM >= OB_TERM_HELD) link_fk(*model, qj, lp, R9);
+        else link_fk(*model, qj, lp);
         double t;
-        if constexpr (CAP) t = capsule_term(T, lp, r + REC_EE, dt, k);
+        if constexpr (TERM == OB_TERM_HELD_SELF) {
+            double Ree[9];
+            grasp_rotation(R9, model->ee_R, Ree);
+            t = held_self_term_at(T, lp, r + REC_EE, Ree);
+        } else if constexpr (TERM == OB_TERM_HELD) t = held_term(T, r + REC_EE, R9, model->ee_R, dt, k);
+        else if constexpr (TERM == OB_TERM_FIELD) t = field_term(T, lp, r + REC_EE);
+        else if constexpr (TERM == OB_TERM_CAPSULES) t = capsule_term(T, lp, r + REC_EE, dt, k);
         else t = obstacle_term(T, lp, r + REC_EE, dt, k);
-        for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
-    }
-    if (lane == 0) *out1 = tot;
-}
-__global__ __launch_bounds__(64) void fr_obstacle_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                               const DevModel *model, double dt, double *out1)
-{
-    obstacle_total<false>(steps, rec, H, compact, model, dt, out1);
-}
-__global__ __launch_bounds__(64) void fr_capsule_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                              const DevModel *model, double dt, double *out1)
-{
-    obstacle_total<true>(steps, rec, H, compact, model, dt, out1);
-}
-
-// The field term of the filter() row the same way (mppi_optimal_field_cost), from the table - and so
-// the grid - of the row's own update
-__global__ __launch_bounds__(64) void fr_field_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                            const DevModel *model, double dt, double *out1)
-{
-    const int lane = threadIdx.x;
-    const ObstacleTableK T = obstacle_table_of(steps, H);
-    double tot = 0.0;
-    for (int base = 0; base < H; base += 64) {
-        const int n = (H - base < 64) ? H - base : 64;
-        const int k = base + (lane < n ? lane : 0);
-        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);
-        double qj[10], lp[SC_LINKS][3];
-        for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
-        link_fk(*model, qj, lp);
-        const double t = field_term(T, lp, r + REC_EE);
-        for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
-    }
-    if (lane == 0) *out1 = tot;
-}
-
-// The held term of the filter() row the same way (mppi_optimal_held_cost), from the table - and so the
-// object and the grid - of the row's own update
-__global__ __launch_bounds__(64) void fr_held_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                           const DevModel *model, double dt, double *out1)
-{
-    const int lane = threadIdx.x;
-    const ObstacleTableK T = obstacle_table_of(steps, H);
-    double tot = 0.0;
-    for (int base = 0; base < H; base += 64) {
-        const int n = (H - base < 64) ? H - base : 64;
-        const int k = base + (lane < n ? lane : 0);
-        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);
-        double qj[10], lp[SC_LINKS][3], R9[9];
-        for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
-        link_fk(*model, qj, lp, R9);
-        const double t = held_term(T, r + REC_EE, R9, model->ee_R, dt, k);
-        for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
-    }
-    if (lane == 0) *out1 = tot;
-}
-
-// The held-self term of the filter() row the same way (mppi_optimal_held_self_cost), from the table - and
-// so the object and the configuration - of the row's own update.  (One wave a launch: the link and held
-// coordinates stay in registers through the pair loop, 256 VGPRs; bounded to its twin's three waves a SIMD it
-// spills 592 bytes a lane.)
-__global__ __launch_bounds__(64) void fr_held_self_total_kernel(const StepConst *steps, const double *rec, int H, int compact,
-                                                                const DevModel *model, double dt, double *out1)
-{
-    const int lane = threadIdx.x;
-    const ObstacleTableK T = obstacle_table_of(steps, H);
-    double tot = 0.0;
-    for (int base = 0; base < H; base += 64) {
-        const int n = (H - base < 64) ? H - base : 64;
-        const int k = base + (lane < n ? lane : 0);
-        const double *r = rec + (int64_t)k * (compact ? FR_REC_C : FR_REC);
-        double qj[10], lp[SC_LINKS][3], R9[9], Ree[9];
-        for (int j = 0; j < 10; j++) qj[j] = lagged_q(r[REC_QQD + 2 * j], r[REC_QQD + 2 * j + 1], dt, k == 0);
-        link_fk(*model, qj, lp, R9);
-        grasp_rotation(R9, model->ee_R, Ree);
-        const double t = held_self_term_at(T, lp, r + REC_EE, Ree);
         for (int i = 0; i < n; i++) tot += readlane_f64(t, i);
     }
     if (lane == 0) *out1 = tot;
@@ -283,6 +182,28 @@ __global__ __launch_bounds__(64) void fr_terms_kernel(const DevCost *cost, const
     }
 }
 
+// One link mode's kernel of the launch's objective and record layout (FrCostArgs::cost_kind, energy, compact:
+// the layout is the launch's that wrote the records).  LINKS: FR_LINKS_ZERO the default mode's kernel, else the
+// links kernel with the obstacle term LINKS - 1 (kernels.hpp).
+using StepCostKernel = void (*)(FrCostArgs);
+template <int LINKS, int CK, bool EN, bool KC>
+constexpr StepCostKernel step_cost_kernel_of()
+{
+    if constexpr (LINKS == FR_LINKS_ZERO) return fr_step_cost_kernel<CK, EN, KC>;
+    else return fr_step_cost_links_kernel<CK, EN, KC, LINKS - 1>;
+}
+template <int LINKS>
+StepCostKernel step_cost_cell(const FrCostArgs &a)
+{
+    if (a.cost_kind == CK_TRACK_POINT)
+        return a.compact ? step_cost_kernel_of<LINKS, CK_TRACK_POINT, false, true>() : step_cost_kernel_of<LINKS, CK_TRACK_POINT, false, false>();
+    if (a.energy)
+        return a.compact ? step_cost_kernel_of<LINKS, CK_ASSISTED_MANIPULATION, true, true>()
+                         : step_cost_kernel_of<LINKS, CK_ASSISTED_MANIPULATION, true, false>();
+    return a.compact ? step_cost_kernel_of<LINKS, CK_ASSISTED_MANIPULATION, false, true>()
+                     : step_cost_kernel_of<LINKS, CK_ASSISTED_MANIPULATION, false, false>();
+}
+
 }  // namespace
 
 namespace mppi_eng {
@@ -300,11 +221,16 @@ hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hip
     return hipGetLastError();
 }
 
-hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                    double dt, double *out1, hipStream_t s, bool capsules)
+hipError_t launch_fr_term_total(int term, const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+                                double dt, double *out1, hipStream_t s)
 {
-    if (capsules) hipLaunchKernelGGL(fr_capsule_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
-    else hipLaunchKernelGGL(fr_obstacle_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
+    using Kernel = void (*)(const StepConst *, const double *, int, int, const DevModel *, double, double *);
+    static constexpr Kernel TOTALS[] = {fr_term_total_kernel<OB_TERM_POINTS>, fr_term_total_kernel<OB_TERM_CAPSULES>,
+                                        fr_term_total_kernel<OB_TERM_FIELD>, fr_term_total_kernel<OB_TERM_HELD>,
+                                        fr_term_total_kernel<OB_TERM_HELD_SELF>};
+    static_assert(sizeof(TOTALS) / sizeof(TOTALS[0]) == OB_TERM_HELD_SELF - OB_TERM_POINTS + 1, "one row a term");
+    if (term < OB_TERM_POINTS || term > OB_TERM_HELD_SELF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(TOTALS[term - OB_TERM_POINTS], dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
     return hipGetLastError();
 }
 
@@ -315,108 +241,22 @@ hipError_t launch_fr_target_total(const DevCost *cost, const StepConst *steps, c
     return hipGetLastError();
 }
 
-hipError_t launch_fr_field_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                 double dt, double *out1, hipStream_t s)
-{
-    hipLaunchKernelGGL(fr_field_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
-    return hipGetLastError();
-}
-
-hipError_t launch_fr_held_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                double dt, double *out1, hipStream_t s)
-{
-    hipLaunchKernelGGL(fr_held_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
-    return hipGetLastError();
-}
-
-hipError_t launch_fr_held_self_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                     double dt, double *out1, hipStream_t s)
-{
-    hipLaunchKernelGGL(fr_held_self_total_kernel, dim3(1), dim3(64), 0, s, steps, rec, H, compact ? 1 : 0, model, dt, out1);
-    return hipGetLastError();
-}
-
 hipError_t launch_fr_step_cost(const FrCostArgs &a, hipStream_t s)
 {
     const int64_t rows = a.count + (a.fcost ? 1 : 0);
     if (rows == 0) return hipSuccess;
-    const dim3 grid((unsigned)rows), block(64);
-    // the records' layout is the launch's that wrote them (FrCostArgs::compact)
-    if (a.link_positions == FR_LINKS_HELD_SELF) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_hs_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.link_positions == FR_LINKS_HELD) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_ho_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.link_positions == FR_LINKS_FIELD) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_df_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.link_positions == FR_LINKS_CAPSULES) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_cap_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.link_positions == FR_LINKS_OBSTACLES) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_ob_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.link_positions) {
-        if (!a.model) return hipErrorInvalidValue;
-        if (a.compact) {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-        } else {
-            if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-            else if (a.energy) hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((fr_step_cost_lp_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
-        }
-    } else if (a.compact) {
-        if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_kernel<CK_TRACK_POINT, false, true>), grid, block, 0, s, a);
-        else if (a.energy) hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, false, true>), grid, block, 0, s, a);
-    } else {
-        if (a.cost_kind == CK_TRACK_POINT) hipLaunchKernelGGL((fr_step_cost_kernel<CK_TRACK_POINT, false, false>), grid, block, 0, s, a);
-        else if (a.energy) hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, true, false>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((fr_step_cost_kernel<CK_ASSISTED_MANIPULATION, false, false>), grid, block, 0, s, a);
+    if (a.link_positions && !a.model) return hipErrorInvalidValue;
+    StepCostKernel kernel;
+    switch (a.link_positions) {
+    case FR_LINKS_ZERO: kernel = step_cost_cell<FR_LINKS_ZERO>(a); break;
+    case FR_LINKS_OBSTACLES: kernel = step_cost_cell<FR_LINKS_OBSTACLES>(a); break;
+    case FR_LINKS_CAPSULES: kernel = step_cost_cell<FR_LINKS_CAPSULES>(a); break;
+    case FR_LINKS_FIELD: kernel = step_cost_cell<FR_LINKS_FIELD>(a); break;
+    case FR_LINKS_HELD: kernel = step_cost_cell<FR_LINKS_HELD>(a); break;
+    case FR_LINKS_HELD_SELF: kernel = step_cost_cell<FR_LINKS_HELD_SELF>(a); break;
+    default: kernel = step_cost_cell<FR_LINKS_KINEMATIC>(a); break;   // and any other nonzero mode
     }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

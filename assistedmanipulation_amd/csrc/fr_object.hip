@@ -444,43 +444,25 @@ __global__ __launch_bounds__(64) void fr_object_kernel(ObjArgs a)
     }
 }
 
-// mppi_dynamics_obstacle_cost: the obstacle term (fr_cost_terms.hpp obstacle_term) at the positions
-// the object cached at its last calculate() - the sphere links PIVOT .. PANDA_LINK7 and the grasp
-// frame - with the table's own time (step 0: tau = t0 - t_ref)
-__global__ __launch_bounds__(64) void fr_object_obstacle_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
+// One obstacle term alone (fr_cost_terms.hpp) at what the object cached at its last calculate() - the sphere
+// links PIVOT .. PANDA_LINK7 and the grasp frame's position and rotation R9 ee_R - with the table's own
+// time (step 0: tau = t0 - t_ref).  TERM: OB_TERM_POINTS obstacle_term (mppi_dynamics_obstacle_cost),
+// OB_TERM_CAPSULES capsule_term (mppi_dynamics_capsule_cost), OB_TERM_FIELD field_term
+// (mppi_dynamics_distance_field_cost), OB_TERM_HELD held_term_at at the grasp frame's pose
+// (mppi_dynamics_held_object_cost), OB_TERM_HELD_SELF held_self_term_at at the link positions and that pose
+// (mppi_dynamics_held_self_cost).
+template <int TERM>
+__global__ __launch_bounds__(64) void fr_object_term_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
 {
+    static_assert(TERM >= OB_TERM_POINTS && TERM <= OB_TERM_HELD_SELF, "no such obstacle term");
     if (threadIdx.x != 0) return;
-    *out1 = mppi_cost::obstacle_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, 0.0, 0);
-}
-
-// mppi_dynamics_capsule_cost: the capsule term (capsule_term) at the same positions
-__global__ __launch_bounds__(64) void fr_object_capsule_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
-{
-    if (threadIdx.x != 0) return;
-    *out1 = mppi_cost::capsule_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, 0.0, 0);
-}
-
-// mppi_dynamics_distance_field_cost: the field term (field_term) at the same positions
-__global__ __launch_bounds__(64) void fr_object_field_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
-{
-    if (threadIdx.x != 0) return;
-    *out1 = mppi_cost::field_term(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION);
-}
-
-// mppi_dynamics_held_object_cost: the held term (held_term_at) at the grasp frame's cached pose - its
-// position and its rotation R9 ee_R as the last calculate() left them
-__global__ __launch_bounds__(64) void fr_object_held_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
-{
-    if (threadIdx.x != 0) return;
-    *out1 = mppi_cost::held_term_at(&t, obj->ee + MPPI_EE_POSITION, obj->ee + MPPI_EE_ROTATION, 0.0, 0);
-}
-
-// mppi_dynamics_held_self_cost: the held-self term (held_self_term_at) at the cached link positions and
-// the grasp frame's cached pose
-__global__ __launch_bounds__(64) void fr_object_held_self_kernel(const DevPinocchio *obj, ObstacleTable t, double *out1)
-{
-    if (threadIdx.x != 0) return;
-    *out1 = mppi_cost::held_self_term_at(&t, obj->link + SC_LINK0, obj->ee + MPPI_EE_POSITION, obj->ee + MPPI_EE_ROTATION);
+    const double (*lp)[3] = obj->link + SC_LINK0;
+    const double *ee = obj->ee + MPPI_EE_POSITION, *Ree = obj->ee + MPPI_EE_ROTATION;
+    if constexpr (TERM == OB_TERM_HELD_SELF) *out1 = mppi_cost::held_self_term_at(&t, lp, ee, Ree);
+    else if constexpr (TERM == OB_TERM_HELD) *out1 = mppi_cost::held_term_at(&t, ee, Ree, 0.0, 0);
+    else if constexpr (TERM == OB_TERM_FIELD) *out1 = mppi_cost::field_term(&t, lp, ee);
+    else if constexpr (TERM == OB_TERM_CAPSULES) *out1 = mppi_cost::capsule_term(&t, lp, ee, 0.0, 0);
+    else *out1 = mppi_cost::obstacle_term(&t, lp, ee, 0.0, 0);
 }
 
 // mppi_dynamics_target_cost: the target-tracking terms (fr_cost_terms.hpp track_point_cost) at the
@@ -503,28 +485,15 @@ hipError_t launch_fr_object_target(const DevPinocchio *obj, const ObjTarget &t, 
     return hipGetLastError();
 }
 
-hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
+hipError_t launch_fr_object_term(int term, const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
 {
-    hipLaunchKernelGGL(fr_object_field_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
-    return hipGetLastError();
-}
-
-hipError_t launch_fr_object_held(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
-{
-    hipLaunchKernelGGL(fr_object_held_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
-    return hipGetLastError();
-}
-
-hipError_t launch_fr_object_held_self(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s)
-{
-    hipLaunchKernelGGL(fr_object_held_self_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
-    return hipGetLastError();
-}
-
-hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s, bool capsules)
-{
-    if (capsules) hipLaunchKernelGGL(fr_object_capsule_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
-    else hipLaunchKernelGGL(fr_object_obstacle_kernel, dim3(1), dim3(64), 0, s, obj, t, out1);
+    using Kernel = void (*)(const DevPinocchio *, ObstacleTable, double *);
+    static constexpr Kernel TERMS[] = {fr_object_term_kernel<OB_TERM_POINTS>, fr_object_term_kernel<OB_TERM_CAPSULES>,
+                                       fr_object_term_kernel<OB_TERM_FIELD>, fr_object_term_kernel<OB_TERM_HELD>,
+                                       fr_object_term_kernel<OB_TERM_HELD_SELF>};
+    static_assert(sizeof(TERMS) / sizeof(TERMS[0]) == OB_TERM_HELD_SELF - OB_TERM_POINTS + 1, "one row a term");
+    if (term < OB_TERM_POINTS || term > OB_TERM_HELD_SELF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(TERMS[term - OB_TERM_POINTS], dim3(1), dim3(64), 0, s, obj, t, out1);
     return hipGetLastError();
 }
 

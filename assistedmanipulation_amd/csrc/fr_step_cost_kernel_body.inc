@@ -1,6 +1,7 @@
-// fr_step_cost_kernel_body.inc - the body of fr_step_cost_kernel and fr_step_cost_lp_kernel
+// fr_step_cost_kernel_body.inc - the body of fr_step_cost_kernel and fr_step_cost_links_kernel
 // (fr_cost.hip); LP (a constexpr bool of the including kernel): the kinematic link-position model;
-// OB (likewise, with LP): the obstacle term (fr_step_cost_ob_kernel).
+// OB (with LP, the links kernel's template parameter): the obstacle term behind it, OB_TERM_NONE ..
+// OB_TERM_HELD_SELF.
     __shared__ double Lj[FR_NB * JT_STRIDE];
     const int lane = threadIdx.x;
     const int64_t row = blockIdx.x;

@@ -126,6 +126,9 @@ static_assert(FR_WRENCH_ROW * sizeof(double) == sizeof(StepConst), "wrench rows 
 // FrRolloutArgs / FrCostArgs::link_positions
 constexpr int FR_LINKS_ZERO = 0, FR_LINKS_KINEMATIC = 1, FR_LINKS_OBSTACLES = 2, FR_LINKS_CAPSULES = 3, FR_LINKS_FIELD = 4, FR_LINKS_HELD = 5,
               FR_LINKS_HELD_SELF = 6;
+static_assert(OB_TERM_NONE == 0 && FR_LINKS_OBSTACLES - 1 == OB_TERM_POINTS && FR_LINKS_CAPSULES - 1 == OB_TERM_CAPSULES &&
+                  FR_LINKS_FIELD - 1 == OB_TERM_FIELD && FR_LINKS_HELD - 1 == OB_TERM_HELD &&
+                  FR_LINKS_HELD_SELF - 1 == OB_TERM_HELD_SELF, "a link mode past the kinematic one is its obstacle term + 1");
 constexpr int FR_TRACE_EXTRA = 128;   // trace slots past the main waves': the relay and the traced relay hosts' tasks
 struct FrRolloutArgs {
     const DevModel *model;
@@ -524,30 +527,14 @@ hipError_t launch_fr_terms(const DevCost *cost, const StepConst *steps, const do
                            hipStream_t s, const DevModel *link_model = nullptr, double dt = 0.0);
 // An update's obstacle table, by value into out (behind the update's step constants, engine_types.hpp)
 hipError_t launch_obstacle_table(const ObstacleTable &t, ObstacleTable *out, hipStream_t s);
-// The obstacle term of one rollout's H records summed over its steps in step order, undiscounted
-// (next to launch_fr_terms' seven totals), from the table behind `steps`
-// (capsules: the capsule term, fr_capsule_total_kernel)
-hipError_t launch_fr_obstacle_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                    double dt, double *out1, hipStream_t s, bool capsules = false);
-// mppi_dynamics_obstacle_cost: the term at the object's cached link and end-effector positions,
-// tau = t.t0 - t.t_ref
-// (capsules: mppi_dynamics_capsule_cost, fr_object_capsule_kernel)
-hipError_t launch_fr_object_obstacles(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s, bool capsules = false);
-// The field term alone: of one rollout's records like launch_fr_obstacle_total (fr_field_total_kernel), and
-// at the object's cached positions (mppi_dynamics_distance_field_cost, fr_object_field_kernel)
-hipError_t launch_fr_field_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                 double dt, double *out1, hipStream_t s);
-hipError_t launch_fr_object_field(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
-// The held term alone (mppi_set_held_object_avoidance) the same two ways: fr_held_total_kernel, and at the
-// object's cached grasp pose (mppi_dynamics_held_object_cost, fr_object_held_kernel)
-hipError_t launch_fr_held_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
+// One obstacle term alone (term: OB_TERM_POINTS .. OB_TERM_HELD_SELF, engine_types.hpp; any other:
+// hipErrorInvalidValue), two ways.  launch_fr_term_total (fr_term_total_kernel): the term of one rollout's H
+// records summed over its steps in step order, undiscounted (next to launch_fr_terms' seven totals), from the
+// table behind `steps`.  launch_fr_object_term (fr_object_term_kernel, the mppi_dynamics_*_cost functions): the
+// term at the object's cached link positions and grasp-frame pose, tau = t.t0 - t.t_ref.
+hipError_t launch_fr_term_total(int term, const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
                                 double dt, double *out1, hipStream_t s);
-hipError_t launch_fr_object_held(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
-// The held-self term alone (mppi_set_held_self_avoidance) the same two ways: fr_held_self_total_kernel, and at
-// the object's cached link positions and grasp pose (mppi_dynamics_held_self_cost, fr_object_held_self_kernel)
-hipError_t launch_fr_held_self_total(const StepConst *steps, const double *rec, int H, bool compact, const DevModel *model,
-                                     double dt, double *out1, hipStream_t s);
-hipError_t launch_fr_object_held_self(const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
+hipError_t launch_fr_object_term(int term, const DevPinocchio *obj, const ObstacleTable &t, double *out1, hipStream_t s);
 
 // Target tracking (mppi_set_target_tracking, mppi_set_target_path): the timed pose path as the host
 // stored it - quaternions normalised and sign-fixed, inv[i] = 1 / (time[i + 1] - time[i]) - and the

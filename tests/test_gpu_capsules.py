@@ -198,7 +198,7 @@ def test_point_only_sets_on_a_capsule_handle(monkeypatch):
 # ---- 3. paths ------------------------------------------------------------------------------------
 
 def test_in_launch_objective_against_the_cost_kernel(monkeypatch):
-    """The same inputs through the launch's own objective and through fr_step_cost_cap_kernel
+    """The same inputs through the launch's own objective and through fr_step_cost_links_kernel<OB_TERM_CAPSULES>
     (MPPI_COSTS_IN_LAUNCH=0), r147_h64, test_gpu_obstacles.py's structure: bit for bit (the two inline
     the same text of the term, and the capsule term's arithmetic is rounded operation by operation)."""
     _, S, H, keep, req, sw, _, _ = by_name("r147_h64")

@@ -200,7 +200,7 @@ def test_simulated_wrench_forecast(monkeypatch):
 # ---- 3. paths ------------------------------------------------------------------------------------
 
 def test_in_launch_objective_against_the_cost_kernel(monkeypatch):
-    """The same inputs through the launch's own objective and through fr_step_cost_df_kernel
+    """The same inputs through the launch's own objective and through fr_step_cost_links_kernel<OB_TERM_FIELD>
     (MPPI_COSTS_IN_LAUNCH=0), r147_h64, test_gpu_capsules.py's structure: bit for bit (the two inline
     the same text of the term, whose arithmetic is rounded operation by operation)."""
     _, S, H, keep, req, sw, _, _ = by_name("r147_h64")
@@ -468,7 +468,7 @@ def test_device_object_field_cost(monkeypatch):
 
 
 def _object_points(obj):
-    """The nine points as the object holds them (what fr_object_field_kernel reads), bit for bit."""
+    """The nine points as the object holds them (what fr_object_term_kernel<OB_TERM_FIELD> reads), bit for bit."""
     return np.concatenate([obj.link_positions()[abi.MPPI_LINK_PIVOT:abi.MPPI_LINK_PIVOT + 8],
                            obj.get_end_effector_state_row()[None, abi.MPPI_EE_POSITION:abi.MPPI_EE_POSITION + 3]])
 

@@ -213,7 +213,7 @@ def test_simulated_wrench_forecast(monkeypatch):
 # ---- 3. paths ------------------------------------------------------------------------------------
 
 def test_in_launch_objective_against_the_cost_kernel(monkeypatch):
-    """The same inputs through the launch's own objective and through fr_step_cost_ho_kernel
+    """The same inputs through the launch's own objective and through fr_step_cost_links_kernel<OB_TERM_HELD>
     (MPPI_COSTS_IN_LAUNCH=0), r147_h64: costs and U* bit for bit."""
     _, S, H, keep, req, sw, _, _ = by_name("r147_h64")
     conf = am.frankaridgeback_configuration(rollouts=S, horison=horizon(H), keep_best_rollouts=keep, threads=8)
